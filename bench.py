@@ -9,15 +9,24 @@
 A "step" is one DDIM denoise step (conditioned UNet evaluation + fused DDIM update) over one batch of
 latents -- BASELINE.json configs[1]: face_reenactment AffectNet emotion-conditioned LDM, DDIM-200 schedule,
 batch 16 per GPU, at the latent size BASELINE.json's metric is quoted on (64x64x4; `--latent 32` selects the
-shipped 32x32x3 shape, which is also measured briefly and reported under "secondary").  Weights are random
+shipped 32x32x3 shape, which --full also measures briefly and reports under "secondary").  Weights are random
 (seeded recipe, dsml_thesis_amd/synth.py: no checkpoints exist offline), inputs synthetic and resident in HBM before
-the timed region.  Prints ONE JSON line on rank 0 (contract in the task statement) including
+the timed region.  Prints ONE JSON line on rank 0 (contract in the task statement).
+
+A plain run does only what the headline needs: set up, warm up, time --steps steps, print the line (`value`,
+`ms_per_step`, ...).  Everything else is measured with --full only (the --no-* switches then pick among the legs):
   roofline     -- the GEMM kernel family (LDS-tiled igemm + row GEMM, f32 MFMA): the FLOPs its launches EXECUTE in one
                   step (sum of 2 M N K over the launch program) divided by their summed durations, measured with HIP
                   events on the launch stream; the reference algorithm's FLOPs are printed beside it
+  secondary, f32_mfma_form, bf16x3_form -- the other latent size and the two other arithmetic forms of the step
   clip         -- BASELINE configs[2]/[3]: the 128-frame talking-face clip (fixed identity) sharded over the ranks, ONE
                   all-gather of the decoded frames inside the timed region, checksum identical for every N
+  batch1, end_to_end, train_bf16 -- the batch-1 autoregressive mode, sample() + decode, one bf16 training step
   cpu_baseline -- the oracle (PyTorch-CPU fp32 restatement of the reference) on this box's host cores, bounded sample
+
+--dump-outputs DIR writes what the timed path returned after its last timed step (rank 0): the DDIM update's x_prev and
+pred_x0 (with --train: the loss and a fixed sample of the updated and EMA parameters) as DIR/<name>.npy, float32.  Inputs
+and weights are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -40,6 +49,20 @@ GFLOP_IGEMM = {32: 24.318 + 15.122 + 2.726, 64: 97.297 + 60.421 + 10.905}   # co
 ALGO_BYTES = {32: lambda b: int(627.0e6 + b * 28e6), 64: lambda b: int(627.0e6 + b * 111e6)}
 PEAK_F32_MFMA = 157.3  # TFLOP/s, MI355X_MICROARCH.md (v_mfma_f32_32x32x2_f32, dense)
 PEAK_BF16_MFMA = 2516.6  # TFLOP/s dense = 16 x the f32 matrix rate (same guide: "1/16 of BF16 MFMA", ~2.5 PF)
+DUMP_BYTES = 64_000_000  # --dump-outputs: all arrays of one run together
+
+
+def save_outputs(path, arrays):
+    """--dump-outputs: every tensor of `arrays` as PATH/<name>.npy, float32.  A tensor larger than its even share of DUMP_BYTES
+    is written as a fixed sample: its flattened elements at the sorted, de-duplicated indices RandomState(0) draws."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // (4 * len(arrays)) - 1024
+    for name, t in arrays.items():
+        x = t.detach().float()
+        if x.numel() > share:
+            idx = np.unique(np.random.RandomState(0).randint(0, x.numel(), size=share, dtype=np.int64))
+            x = x.reshape(-1)[torch.from_numpy(idx).to(x.device)]
+        np.save(os.path.join(path, f"{name}.npy"), x.cpu().numpy())
 
 
 def build_model(latent, device):
@@ -506,6 +529,9 @@ def train_measure(a, latent, rank, world, dev, dist, backend, barrier, graph):
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         el = tt.item()
     assert torch.isfinite(loss_buf).all()
+    if rank == 0 and getattr(a, "dump_outputs", None):
+        # what the last timed step handed back: its loss and the weights after AdamW + EMA (flat packed layout)
+        save_outputs(a.dump_outputs, {"loss": loss_buf, "params": tr.P.flat, "ema_params": shadow})
     fwd_gemm = (42.17 if latent == 32 else 168.62) * 1e9 * n
     fwd_attn = (3.84 if latent == 32 else 61.43) * 1e9 * n
     flops = world * (3 * fwd_gemm + 3.5 * fwd_attn)
@@ -555,7 +581,14 @@ def main():
     ap.add_argument("--train", action="store_true",
                     help="measure BASELINE configs[4] instead (UNet p_losses forward+backward+AdamW+EMA, fp32, data-"
                          "parallel with one all-reduce of the flat gradient buffer); not the default metric")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, measure the roofline, the secondary latent, the other arithmetic forms, the clip / "
+                         "batch-1 / end-to-end / training legs and the CPU baseline (the --no-* switches pick among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned after its last timed step as DIR/<name>.npy (float32, rank 0)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.clip_steps is None:
         a.clip_steps = 200
 
@@ -673,7 +706,10 @@ def main():
         "batch_steps_per_s": round(world * a.steps / el, 3),
         "step_tflops": round(world * GFLOP_STEP[a.latent] * a.batch * 1e-3 / (ms * 1e-3), 2),
     }
-    if rank == 0:
+    if rank == 0 and a.dump_outputs:
+        # what p_sample_ddim hands back for the last timed step: x_{t-1} and pred_x0 (batch x C x H x W)
+        save_outputs(a.dump_outputs, {"x_prev": run.pg.inputs["x"], "pred_x0": run.pred_x0})
+    if rank == 0 and a.full:
         t_ig, n_ig = run.igemm_time_per_step()
         fl_exec = executed_gemm_flops(run.pg) * 1e-12             # TFLOP the GEMM launches of one step execute
         ach = fl_exec / (t_ig * 1e-3)
@@ -766,7 +802,7 @@ def main():
             r["by_arithmetic"] = split
     del run
     torch.cuda.empty_cache()
-    if not a.no_secondary and world == 1:
+    if a.full and not a.no_secondary and world == 1:
         other = 32 if a.latent == 64 else 64
         run2, el2 = measure(other, max(5, a.steps // 2), 2, graph)
         out["secondary"] = {"workload": f"same, {other}x{other}x{run2.x_T.shape[1]} latent",
@@ -804,7 +840,7 @@ def main():
                 finally:
                     del os.environ["LDMK_F16X2"]
                     _eng.reset_tables()
-    if not a.no_clip:
+    if a.full and not a.no_clip:
         torch.cuda.empty_cache()
         out["clip"] = clip_leg(rank, world, dev, dist, barrier, frames=a.clip_frames, ddim_steps=a.clip_steps, policy=a.clip_policy)
         if rank == 0 and world == 1 and a.clip_frames >= 64 and not a.no_extras:
@@ -815,7 +851,7 @@ def main():
         if rank == 0 and world == 1:
             torch.cuda.empty_cache()
             out["batch1"] = batch1_leg(dev)
-    if rank == 0 and world == 1 and not a.no_extras:
+    if a.full and rank == 0 and world == 1 and not a.no_extras:
         # BASELINE configs[1] end to end and configs[4] (one GPU: forward + backward + AdamW + EMA, bf16 matrix-core compute)
         torch.cuda.empty_cache()
         out["end_to_end"] = end_to_end_leg(dev, a.latent, a.batch)
@@ -826,7 +862,7 @@ def main():
         tb = train_measure(_T, a.latent, rank, world, dev, None, backend, barrier, graph)
         out["train_bf16"] = {k: tb[k] for k in ("metric", "value", "unit", "ms_per_step", "steps", "dtype", "config", "step_tflops", "roofline", "loss")}
         torch.cuda.empty_cache()
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(a.latent)
     elif rank == 0:
         out["cpu_baseline"] = None

@@ -64,28 +64,70 @@ def _contract(d, split):
 
 
 def test_bench_line_has_the_contract_fields():
-    d = _run("--steps", "3", "--warmup", "1", "--no-secondary", "--no-cpu-baseline", "--no-clip", "--no-extras")
+    d = _run("--full", "--steps", "3", "--warmup", "1", "--no-secondary", "--no-cpu-baseline", "--no-clip", "--no-extras")
     _contract(d, split="f16x2")
     # value is consistent with the timed region: batch * steps / time
     assert abs(d["value"] - d["config"]["global_batch"] * 1e3 / d["ms_per_step"]) / d["value"] < 1e-3
 
 
+def test_plain_line_is_the_headline_alone_and_dumps_the_last_step(tmp_path):
+    """Without --full the run times the headline and nothing else; --dump-outputs writes the last timed step's x_prev and
+    pred_x0.  The inputs are seeded, so two runs with the same arguments return the same arrays; and a run one step shorter
+    dumps the INPUT of that last step, from which the DDIM update (eta 0) must give exactly the dumped x_prev / pred_x0 pair."""
+    import numpy as np
+    from dsml_thesis_amd import schedule as S
+    from dsml_thesis_amd import synth
+    base = json.load(open(os.path.join(ROOT, "BASELINE.json")))
+    dumps = []
+    for name, steps in (("a", "3"), ("b", "3"), ("c", "2")):
+        d = _run("--steps", steps, "--warmup", "1", "--dump-outputs", str(tmp_path / name))
+        assert d["metric"] == base["metric"] and d["unit"] == "sample-steps/s" and d["dtype"] == "f32" and d["higher_is_better"] is True
+        assert d["steps"] == int(steps) and d["warmup"] == 1 and d["n_gpus"] == 1
+        assert abs(d["value"] - d["config"]["global_batch"] * 1e3 / d["ms_per_step"]) / d["value"] < 1e-3
+        for k in ("roofline", "secondary", "f32_mfma_form", "bf16x3_form", "clip", "batch1", "end_to_end", "train_bf16"):
+            assert k not in d, k
+        assert d["cpu_baseline"] is None
+        dumps.append({k: np.load(tmp_path / name / f"{k}.npy") for k in ("x_prev", "pred_x0")})
+    for k, v in dumps[0].items():
+        assert v.dtype == np.float32 and v.shape == (16, 4, 64, 64) and np.isfinite(v).all(), k
+        np.testing.assert_allclose(dumps[1][k], v, rtol=1e-5, atol=1e-5, err_msg=k)
+    # not the seeded start latent (bench.py StepRunner: RandomState(1) on rank 0)
+    x_T = np.random.RandomState(1).standard_normal((16, 4, 64, 64)).astype(np.float32)
+    assert np.abs(dumps[0]["x_prev"] - x_T).max() > 1e-2
+    # warmup 1 + 3 timed steps of DDIM-200 walk the step index 199, 198, 197, 196: the 2-step run's x_prev is the input x of
+    # step 196.  eps follows from that input and pred_x0 = (x - sqrt(1 - a_t) eps) / sqrt(a_t), and the update must reproduce
+    # x_prev = sqrt(a_prev) pred_x0 + sqrt(1 - a_prev) eps
+    ac = S.schedule_buffers(S.make_beta_schedule("linear", synth.SCHEDULE["timesteps"], linear_start=synth.SCHEDULE["linear_start"],
+                                                 linear_end=synth.SCHEDULE["linear_end"]))["alphas_cumprod"]
+    a_t, a_prev, sigma, s1m = S.ddim_step_table(ac, S.make_ddim_timesteps("uniform", 200, 1000), 0.0)[196].astype(np.float64)
+    assert sigma == 0.0
+    x_in, p0 = dumps[2]["x_prev"].astype(np.float64), dumps[0]["pred_x0"].astype(np.float64)
+    eps = (x_in - np.sqrt(a_t) * p0) / s1m
+    np.testing.assert_allclose(dumps[0]["x_prev"], np.sqrt(a_prev) * p0 + np.sqrt(1.0 - a_prev) * eps, rtol=1e-4, atol=1e-3)
+    assert np.abs(dumps[0]["x_prev"] - x_in).max() > 1e-2        # and the last step did move the latent
+
+
 def test_bench_line_f32_matrix_core_form():
     """LDMK_SPLIT_BF16=0: every GEMM on v_mfma_f32_32x32x2_f32, priced against the f32 matrix peak."""
-    d = _run("--steps", "3", "--warmup", "1", "--no-secondary", "--no-cpu-baseline", "--no-clip", "--no-extras", env={"LDMK_SPLIT_BF16": "0"})
+    d = _run("--full", "--steps", "3", "--warmup", "1", "--no-secondary", "--no-cpu-baseline", "--no-clip", "--no-extras", env={"LDMK_SPLIT_BF16": "0"})
     _contract(d, split=False)
 
 
 def test_bench_line_bf16x3_form():
     """LDMK_F16X2=0: the round-3 arithmetic (six bf16 MFMAs per product), priced on the bf16 MFMA FLOPs it issues."""
-    d = _run("--steps", "3", "--warmup", "1", "--no-secondary", "--no-cpu-baseline", "--no-clip", "--no-extras", env={"LDMK_F16X2": "0"})
+    d = _run("--full", "--steps", "3", "--warmup", "1", "--no-secondary", "--no-cpu-baseline", "--no-clip", "--no-extras", env={"LDMK_F16X2": "0"})
     _contract(d, split="bf16x3")
 
 
-def test_bench_train_mode_line():
-    d = _run("--train", "--steps", "2", "--warmup", "1", "--batch", "4")
+def test_bench_train_mode_line(tmp_path):
+    d = _run("--train", "--steps", "2", "--warmup", "1", "--batch", "4", "--dump-outputs", str(tmp_path))
     assert d["unit"] == "samples/s" and d["n_gpus"] == 1 and d["dtype"] == "f32" and d["value"] > 1
     assert d["roofline"]["bound"] == "mfma" and 0.0 < d["roofline"]["frac"] < 1.0
+    # --dump-outputs: the last step's loss and (a fixed sample of) the weights after AdamW + EMA, float32, within 64 MB
+    import numpy as np
+    out = {k: np.load(tmp_path / f"{k}.npy") for k in ("loss", "params", "ema_params")}
+    assert out["loss"].shape == (1,) and all(v.dtype == np.float32 and v.size and np.isfinite(v).all() for v in out.values())
+    assert sum(os.path.getsize(tmp_path / f) for f in os.listdir(tmp_path)) <= 64_000_000
     b = _run("--train", "--bf16", "--steps", "2", "--warmup", "1", "--batch", "4")
     assert b["dtype"] == "bf16" and b["value"] > 1 and "bf16 matrix-core" in b["config"]["workload"]
     assert b["roofline"]["peak"] > 2000 and d["roofline"]["peak"] < 200      # each priced against its own arithmetic's peak
@@ -94,7 +136,7 @@ def test_bench_train_mode_line():
 def test_bench_self_launches_two_ranks_and_the_clip_checksum_does_not_depend_on_the_rank_count():
     """`python bench.py --gpus 2` starts its own ranks (here both on the one GPU, gloo collectives): n_gpus = 2, the clip
     leg runs sharded with its all-gather inside the timed region, and its checksum equals the 1-rank run's bit for bit."""
-    flags = ("--steps", "2", "--warmup", "1", "--batch", "2", "--latent", "32", "--no-secondary", "--no-cpu-baseline",
+    flags = ("--full", "--steps", "2", "--warmup", "1", "--batch", "2", "--latent", "32", "--no-secondary", "--no-cpu-baseline",
              "--clip-frames", "6", "--clip-steps", "4", "--no-extras", "--clip-policy", "job")
     one = _run(*flags)
     two = _run("--gpus", "2", *flags, env={"LDMK_BENCH_BACKEND": "gloo"})
@@ -112,7 +154,7 @@ def test_rccl_rehearsal_one_rank_issues_the_real_all_gather_next_to_a_live_hipgr
     LDMK_BENCH_FORCE_DIST=1 the one-rank bench creates the nccl (= RCCL) process group, and the clip leg issues the REAL
     `all_gather_into_tensor` on the decoded device frames inside each timed job -- between hipGraph replays of the DDIM step
     (parallel.all_gather_items: the world-1 short cut is off under LDMK_FORCE_COLLECTIVE).  Same frames as without it."""
-    flags = ("--steps", "2", "--warmup", "1", "--batch", "2", "--latent", "32", "--no-secondary", "--no-cpu-baseline",
+    flags = ("--full", "--steps", "2", "--warmup", "1", "--batch", "2", "--latent", "32", "--no-secondary", "--no-cpu-baseline",
              "--clip-frames", "6", "--clip-steps", "4", "--no-extras", "--clip-policy", "job")
     plain = _run(*flags)
     assert plain["clip"]["ranks_seen"] == 1 and plain["clip"]["collectives_issued_in_timed_jobs"] == 0 and plain["clip"]["backend"] is None
@@ -125,10 +167,10 @@ def test_rccl_rehearsal_one_rank_issues_the_real_all_gather_next_to_a_live_hipgr
 
 
 def test_default_line_carries_every_baseline_config():
-    """The driver's one line (default legs, short timed region): configs[1] headline + its end-to-end sample() + decode at CFG
+    """The --full line (default legs, short timed region): configs[1] headline + its end-to-end sample() + decode at CFG
     1.0 and 3.0, configs[2] the 128-frame clip AT ITS SHIPPED DDIM-200, the reference's batch-1 autoregressive mode and its
     16-clip lock-step form, configs[4] one GPU of the bf16 training step with its own roofline."""
-    d = _run("--steps", "3", "--warmup", "1", "--no-secondary", "--no-cpu-baseline")
+    d = _run("--full", "--steps", "3", "--warmup", "1", "--no-secondary", "--no-cpu-baseline")
     assert d["clip"]["ddim_steps"] == 200 and d["clip"]["frames"] == 128 and d["clip"]["frames_per_s"] > 5
     b1 = d["batch1"]
     assert b1["ms_per_step"] < 10 and b1["clips16"]["clips"] == 16 and b1["clips16"]["sample_steps_per_s"] > 2 * b1["sample_steps_per_s"]

@@ -4,7 +4,7 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import golden
+from conftest import GOLDEN, golden
 from oracle import weights as W
 
 
@@ -291,12 +291,11 @@ def test_gradient_bucket_plan():
         plan_buckets([500, 800, 0], 1000, 100)
 
 
-# ---- the shipped YAMLs (container only: /root/reference does not travel to the GPU box) -----------------------------
-_REF = "/root/reference"
+# ---- the shipped YAMLs: the `model` section of each, stored under tests/golden/configs/ ----------------------------
 _YAMLS = {
-    "fr": "face_reenactment/configs/latent-diffusion/affectnet-128-ldm-vq-f4.yaml",
-    "fr_clip": "face_reenactment/configs/latent-diffusion/affectnet-128-clip-ldm-vq-f4.yaml",
-    "tf": "talking_face/configs/latent-diffusion/mead-128-ldm-f4.yaml",
+    "fr": "affectnet-128-ldm-vq-f4.yaml",          # face_reenactment/configs/latent-diffusion/
+    "fr_clip": "affectnet-128-clip-ldm-vq-f4.yaml",  # face_reenactment/configs/latent-diffusion/
+    "tf": "mead-128-ldm-f4.yaml",                  # talking_face/configs/latent-diffusion/
 }
 
 
@@ -309,7 +308,6 @@ def _strip_ckpt(node):
     return node
 
 
-@pytest.mark.skipif(not __import__("os").path.isdir(_REF), reason="the reference tree exists only in the build container")
 @pytest.mark.parametrize("which", sorted(_YAMLS))
 def test_shipped_yaml_instantiates_and_matches_the_enumerated_layout(which):
     """the YAML `target:` factory is the drop-in boundary.  The three shipped model configs are read with
@@ -319,7 +317,7 @@ def test_shipped_yaml_instantiates_and_matches_the_enumerated_layout(which):
     import os
     from dsml_thesis_amd import synth
     from dsml_thesis_amd.util import instantiate_from_config, load_yaml_config
-    cfg = _strip_ckpt(load_yaml_config(os.path.join(_REF, _YAMLS[which])))["model"]
+    cfg = _strip_ckpt(load_yaml_config(os.path.join(GOLDEN, "configs", _YAMLS[which])))["model"]
     params = cfg["params"]
     ucfg, fcfg = params["unet_config"]["params"], params["first_stage_config"]["params"]
     want_unet = W.TF_UNET if which == "tf" else W.FR_UNET
@@ -440,3 +438,21 @@ def test_sampler_conditioning_forms():
     for form in (y, [y], {"c_crossattn": [y]}):
         lab, none = s._split_cond(form)
         assert lab is y and none is None
+
+
+def test_bench_dump_outputs_budget_and_fixed_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float32 .npy per array; an array over its share of the byte budget is written as a seeded
+    sample, the same one every time, and the files stay within the budget."""
+    import os
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BYTES", 64 * 1024)
+    small = torch.arange(12, dtype=torch.float64).reshape(3, 4)
+    big = torch.randn(100_000, generator=torch.Generator().manual_seed(0))
+    for d in ("a", "b"):
+        bench.save_outputs(str(tmp_path / d), {"small": small, "big": big})
+    s = np.load(tmp_path / "a" / "small.npy")
+    assert s.dtype == np.float32 and s.shape == (3, 4) and np.array_equal(s, small.numpy().astype(np.float32))
+    b = np.load(tmp_path / "a" / "big.npy")
+    assert b.dtype == np.float32 and 0 < b.size <= bench.DUMP_BYTES // 8 and np.isin(b, big.numpy()).all()
+    assert np.array_equal(b, np.load(tmp_path / "b" / "big.npy"))
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= bench.DUMP_BYTES

@@ -172,7 +172,7 @@ def test_g11_northstar_shapes():
     assert np.array_equal(idx.reshape(-1).numpy(), g["vq4_idx"].reshape(-1))
     close(zq, g["vq4_zq"], 0, 0)
     img, _ = O.decode_first_stage(vsd, W.VQ_F4_256, z)
-    close(img, g["decoded256"], 1e-4, 2e-4)
+    close(img, golden("g11_northstar_decoded256.npz")["decoded256"], 1e-4, 2e-4)
     vsd128 = recipe(W.vqmodel_param_shapes(W.VQ_F4))
     img128, _ = O.decode_first_stage(vsd128, W.VQ_F4, rnd(61, 1, 3, 32, 32))
     close(img128, g["decoded128"], 1e-4, 2e-4)

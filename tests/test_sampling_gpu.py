@@ -594,8 +594,8 @@ def test_northstar_trajectory_and_decode_golden():
     z = rnd(112, 1, 4, 64, 64).cuda()
     img, idx = m.first_stage_model.decode(z, return_indices=True)
     assert np.array_equal(idx.cpu().numpy(), g["vq4_idx"].reshape(-1))
-    close(img, g["decoded256"], 1e-4, 1e-4)
-    close(m.decode_first_stage(z, force_not_quantize=True), g["decoded256_noquant"], 1e-4, 1e-4)
+    close(img, golden("g11_northstar_decoded256.npz")["decoded256"], 1e-4, 1e-4)
+    close(m.decode_first_stage(z, force_not_quantize=True), golden("g11_northstar_decoded256_noquant.npz")["decoded256_noquant"], 1e-4, 1e-4)
 
 
 def test_northstar_trajectory_in_the_split_arithmetic(monkeypatch):

@@ -10,7 +10,7 @@ for v in 0 1; do
 done
 for rep in 1 2; do for v in 0 1; do
   echo "== step, LDMK_PS_LEAN=$v (round $rep)" >> $out
-  LDMK_PS_LEAN=$v python bench.py --no-cpu-baseline --no-clip --no-extras --steps 100 --warmup 20 2>/dev/null | python -c "
+  LDMK_PS_LEAN=$v python bench.py --full --no-cpu-baseline --no-clip --no-extras --steps 100 --warmup 20 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.readlines()[-1]); print('  64x64x4', d['value'], ' 32x32x3', d.get('secondary',{}).get('value'))" >> $out
 done; done

@@ -12,7 +12,7 @@ done
 for rep in 1 2; do
   for p in 0 1 2; do
     echo "== step, LDMK_ATTN_PIPE=$p (round $rep)" >> $out
-    LDMK_ATTN_PIPE=$p python bench.py --no-cpu-baseline --no-clip --no-extras --steps 100 --warmup 20 2>/dev/null | python -c "
+    LDMK_ATTN_PIPE=$p python bench.py --full --no-cpu-baseline --no-clip --no-extras --steps 100 --warmup 20 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.readlines()[-1]); print('  64x64x4', d['value'], ' 32x32x3', d.get('secondary',{}).get('value'))" >> $out || exit 1
   done

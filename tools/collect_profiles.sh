@@ -9,9 +9,9 @@ O=$R/gpurun_out/r05p
 PART=${PART:-123}
 mkdir -p $O
 if [[ $PART == *1* ]]; then
-python3 $R/bench.py > $O/r05_bench_default.json 2> $O/bench_default.err
+python3 $R/bench.py --full > $O/r05_bench_default.json 2> $O/bench_default.err
 fi
-B="python3 $R/bench.py --no-secondary --no-cpu-baseline --no-clip --no-extras"
+B="python3 $R/bench.py --full --no-secondary --no-cpu-baseline --no-clip --no-extras"
 prof() {
   lat=$1
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/ks$lat -- $B --latent $lat > $O/r05_bench${lat}_under_rocprof.json 2> $O/ks$lat.log

@@ -662,6 +662,9 @@ def gen_northstar():
     mine, _ = O.decode_first_stage(vsd128, W.VQ_F4, z128)
     check("decode_first_stage 128^2", ref, mine, 1e-4, 2e-4)
     g["decoded128"] = ref
+    # each 256^2 frame in a file of its own: no fixture above 1 MiB
+    save("g11_northstar_decoded256.npz", decoded256=g.pop("decoded256"))
+    save("g11_northstar_decoded256_noquant.npz", decoded256_noquant=g.pop("decoded256_noquant"))
     save("g11_northstar.npz", **g)
 
 
