@@ -18,12 +18,9 @@
 //     product, provided the A operand enumerates the contraction index in the same order; the transposed image serves that
 //     order as two runs of four.
 #include "ldmk_common.h"
-#include <type_traits>
+#include "ldmk_split.h"
 
 namespace ldmk {
-
-typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 
 constexpr int BA_D = 32;
 constexpr int BA_T = 64;            // rows per staged tile
@@ -31,11 +28,11 @@ constexpr int BA_RS = 40;           // row-major image: bf16 per row (80 B: 16-b
 constexpr int BA_TS = 72;           // transposed image: bf16 per d row (144 B)
 constexpr int BA_FS = 33;           // fp32 transpose buffer stride (output rows)
 
-__device__ __forceinline__ bf16x8_t pack8(const float* v) {
-  return bf16x8_t{(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3], (__bf16)v[4], (__bf16)v[5], (__bf16)v[6], (__bf16)v[7]};
+__device__ __forceinline__ bf16x8 pack8(const float* v) {
+  return bf16x8{(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3], (__bf16)v[4], (__bf16)v[5], (__bf16)v[6], (__bf16)v[7]};
 }
-__device__ __forceinline__ bf16x8_t pack8(const f32x16& a, int t) {
-  return bf16x8_t{(__bf16)a[8 * t], (__bf16)a[8 * t + 1], (__bf16)a[8 * t + 2], (__bf16)a[8 * t + 3],
+__device__ __forceinline__ bf16x8 pack8(const f32x16& a, int t) {
+  return bf16x8{(__bf16)a[8 * t], (__bf16)a[8 * t + 1], (__bf16)a[8 * t + 2], (__bf16)a[8 * t + 3],
                   (__bf16)a[8 * t + 4], (__bf16)a[8 * t + 5], (__bf16)a[8 * t + 6], (__bf16)a[8 * t + 7]};
 }
 
@@ -51,24 +48,24 @@ __device__ __forceinline__ void stage_bf16(__bf16* R, __bf16* T, const float* __
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     const int row = rr + 32 * i;
-    const bf16x4_t b = {(__bf16)v[i].x, (__bf16)v[i].y, (__bf16)v[i].z, (__bf16)v[i].w};
-    if (R) *reinterpret_cast<bf16x4_t*>(R + row * BA_RS + d4) = b;
+    const bf16x4 b = {(__bf16)v[i].x, (__bf16)v[i].y, (__bf16)v[i].z, (__bf16)v[i].w};
+    if (R) *reinterpret_cast<bf16x4*>(R + row * BA_RS + d4) = b;
     if (T) { T[(d4 + 0) * BA_TS + row] = b[0]; T[(d4 + 1) * BA_TS + row] = b[1]; T[(d4 + 2) * BA_TS + row] = b[2]; T[(d4 + 3) * BA_TS + row] = b[3]; }
   }
 }
 
 // A operand from the row-major image: rows sub*32 + l31, contraction index d = 16 t + 8 half .. + 7
-__device__ __forceinline__ bf16x8_t op_rows(const __bf16* R, int sub, int l31, int half, int t) {
-  return *reinterpret_cast<const bf16x8_t*>(R + (sub * 32 + l31) * BA_RS + 16 * t + 8 * half);
+__device__ __forceinline__ bf16x8 op_rows(const __bf16* R, int sub, int l31, int half, int t) {
+  return *reinterpret_cast<const bf16x8*>(R + (sub * 32 + l31) * BA_RS + 16 * t + 8 * half);
 }
 // A operand from the transposed image: row d = l31, contraction index = tile rows sub*32 + 16 t + 4 half + (j&3) + 8 (j>>2)
-__device__ __forceinline__ bf16x8_t op_cols(const __bf16* T, int sub, int l31, int half, int t) {
+__device__ __forceinline__ bf16x8 op_cols(const __bf16* T, int sub, int l31, int half, int t) {
   const __bf16* p = T + l31 * BA_TS + sub * 32 + 16 * t + 4 * half;
-  const bf16x4_t lo = *reinterpret_cast<const bf16x4_t*>(p), hi = *reinterpret_cast<const bf16x4_t*>(p + 8);
-  return bf16x8_t{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+  const bf16x4 lo = *reinterpret_cast<const bf16x4*>(p), hi = *reinterpret_cast<const bf16x4*>(p + 8);
+  return bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
 }
 // register fragment (B operand): row `rowp` of a [rows][ld] fp32 matrix, d = 16 t + 8 half .. + 7, scaled
-__device__ __forceinline__ void frag_rows(bf16x8_t (&f)[2], const float* __restrict__ rowp, int half, float mul) {
+__device__ __forceinline__ void frag_rows(bf16x8 (&f)[2], const float* __restrict__ rowp, int half, float mul) {
 #pragma unroll
   for (int t = 0; t < 2; ++t) {
     const float4 a = *reinterpret_cast<const float4*>(rowp + 16 * t + 8 * half), b = *reinterpret_cast<const float4*>(rowp + 16 * t + 8 * half + 4);
@@ -76,7 +73,7 @@ __device__ __forceinline__ void frag_rows(bf16x8_t (&f)[2], const float* __restr
     f[t] = pack8(v);
   }
 }
-__device__ __forceinline__ f32x16 mm(const bf16x8_t a, const bf16x8_t b, const f32x16 c) {
+__device__ __forceinline__ f32x16 mm(const bf16x8 a, const bf16x8 b, const f32x16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }
 
@@ -107,7 +104,7 @@ __global__ __launch_bounds__(256) void attn_bf16_fwd_kernel(const float* __restr
   const float* base = qkv + (long long)b * tokens * ld;
   const bool wave_active = q0 < tokens;
   const bool q_valid = q0 + l31 < tokens;
-  bf16x8_t qf[2];
+  bf16x8 qf[2];
   frag_rows(qf, base + (long long)(q_valid ? q0 + l31 : 0) * ld + h * BA_D, half, q_valid ? scale : 0.f);
   f32x16 o;
 #pragma unroll
@@ -173,7 +170,7 @@ __global__ __launch_bounds__(256) void attn_bf16_dq_kernel(const float* __restri
   const bool wave_active = q0 < tokens;
   const bool q_valid = q0 + l31 < tokens;
   const int qq = q_valid ? q0 + l31 : 0;
-  bf16x8_t qf[2], dof[2];
+  bf16x8 qf[2], dof[2];
   frag_rows(qf, base + (long long)qq * ld + h * BA_D, half, q_valid ? scale : 0.f);
   frag_rows(dof, dout + ((long long)b * tokens + qq) * C + h * BA_D, half, q_valid ? 1.f : 0.f);
   const float Lq = q_valid ? lse[((long long)b * heads + h) * tokens + qq] : INFINITY;
@@ -233,7 +230,7 @@ __global__ __launch_bounds__(256) void attn_bf16_dkv_kernel(const float* __restr
   const bool wave_active = k0 < tokens;
   const bool k_valid = k0 + l31 < tokens;
   const int kk = k_valid ? k0 + l31 : 0;
-  bf16x8_t kf[2], vf[2];
+  bf16x8 kf[2], vf[2];
   frag_rows(kf, base + (long long)kk * ld + C + h * BA_D, half, k_valid ? scale : 0.f);
   frag_rows(vf, base + (long long)kk * ld + 2 * C + h * BA_D, half, k_valid ? 1.f : 0.f);
   f32x16 dk, dv;
@@ -294,13 +291,7 @@ void attn_rowdot_launch(const float* dout, const float* out, float* dsum, int to
 // step is 24 bf16 MFMAs of 32 cycles (768) where the fp32 form issues 32 of 64 (2048); softmax, running statistics and the
 // output stay fp32.  Same tile walk and operand orders as attn_bf16_fwd_kernel above; K / V tiles hold three images each.
 __device__ __forceinline__ float bfu(__bf16 b) { return (float)b; }
-__device__ __forceinline__ void split4(const float4& v, bf16x4_t& h, bf16x4_t& m, bf16x4_t& l) {
-  h = bf16x4_t{(__bf16)v.x, (__bf16)v.y, (__bf16)v.z, (__bf16)v.w};
-  const float r0 = v.x - bfu(h[0]), r1 = v.y - bfu(h[1]), r2 = v.z - bfu(h[2]), r3 = v.w - bfu(h[3]);
-  m = bf16x4_t{(__bf16)r0, (__bf16)r1, (__bf16)r2, (__bf16)r3};
-  l = bf16x4_t{(__bf16)(r0 - bfu(m[0])), (__bf16)(r1 - bfu(m[1])), (__bf16)(r2 - bfu(m[2])), (__bf16)(r3 - bfu(m[3]))};
-}
-__device__ __forceinline__ void split8(const float* v, bf16x8_t (&o)[3]) {
+__device__ __forceinline__ void split8(const float* v, bf16x8 (&o)[3]) {
   float r[8];
   o[0] = pack8(v);
 #pragma unroll
@@ -311,7 +302,7 @@ __device__ __forceinline__ void split8(const float* v, bf16x8_t (&o)[3]) {
   o[2] = pack8(r);
 }
 // the six partial products, smallest first (images: 0 = hi, 1 = mid, 2 = lo)
-__device__ __forceinline__ f32x16 mm6(const bf16x8_t (&a)[3], const bf16x8_t (&b)[3], f32x16 c) {
+__device__ __forceinline__ f32x16 mm6(const bf16x8 (&a)[3], const bf16x8 (&b)[3], f32x16 c) {
   c = mm(a[2], b[0], c);
   c = mm(a[0], b[2], c);
   c = mm(a[1], b[1], c);
@@ -329,7 +320,6 @@ __device__ __forceinline__ f32x16 mm6(const bf16x8_t (&a)[3], const bf16x8_t (&b
 //    query column always sees at least one unmasked key, so no NaN can arise),
 //  * the bf16 images of a pair of probabilities are one v_cvt_pk_bf16_f32 each, widened back with a shift / a mask.
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4a __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void both_halves(float x, float& a, float& b) {       // a, b = the value of lane l31 / of lane l31 + 32
   const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
   a = __uint_as_float(r[0]);
@@ -376,8 +366,8 @@ __device__ __forceinline__ void x3_softmax(f32x16& s, f32x16& o, float& m_run, f
   l_run += a + b;
 }
 // probabilities s[8 t .. 8 t + 7] as their three bf16 images (the exact split of split8, two elements per operation)
-__device__ __forceinline__ void split_p8(const f32x16& s, int t, bf16x8_t (&o)[3]) {
-  u32x4a h, m, l;
+__device__ __forceinline__ void split_p8(const f32x16& s, int t, bf16x8 (&o)[3]) {
+  u32x4 h, m, l;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const f32x2 p = {s[8 * t + 2 * j], s[8 * t + 2 * j + 1]};
@@ -386,9 +376,9 @@ __device__ __forceinline__ void split_p8(const f32x16& s, int t, bf16x8_t (&o)[3
     m[j] = cvt_pk_bf16(r);
     l[j] = cvt_pk_bf16(r - widen_pk_bf16(m[j]));
   }
-  o[0] = __builtin_bit_cast(bf16x8_t, h);
-  o[1] = __builtin_bit_cast(bf16x8_t, m);
-  o[2] = __builtin_bit_cast(bf16x8_t, l);
+  o[0] = __builtin_bit_cast(bf16x8, h);
+  o[1] = __builtin_bit_cast(bf16x8, m);
+  o[2] = __builtin_bit_cast(bf16x8, l);
 }
 
 constexpr int X3_KIMG = BA_T * BA_RS, X3_VIMG = BA_D * BA_TS;       // bf16 elements per K / V image
@@ -409,7 +399,7 @@ __global__ __launch_bounds__(256) void attn_x3_fwd_kernel(const float* __restric
   const bool q_valid = q0 + l31 < tokens;
   constexpr float LOG2E = 1.4426950408889634f;
   // Q fragments (B operand of S^T = K Q^T), pre-scaled by scale * log2(e) in fp32 (scores live in the log2 domain), then split
-  bf16x8_t qf[2][3];
+  bf16x8 qf[2][3];
   {
     const float* rowp = base + (long long)(q_valid ? q0 + l31 : 0) * ld + h * BA_D;
     const float mul = q_valid ? scale * LOG2E : 0.f;
@@ -446,11 +436,11 @@ __global__ __launch_bounds__(256) void attn_x3_fwd_kernel(const float* __restric
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int row = rr + 32 * i;
-      bf16x4_t g[3];
-      split4(kreg[i], g[0], g[1], g[2]);
+      bf16x4 g[3];
+      split3(kreg[i], g[0], g[1], g[2]);
 #pragma unroll
-      for (int q = 0; q < 3; ++q) *reinterpret_cast<bf16x4_t*>(Kr + q * X3_KIMG + row * BA_RS + d4) = g[q];
-      split4(vreg[i], g[0], g[1], g[2]);
+      for (int q = 0; q < 3; ++q) *reinterpret_cast<bf16x4*>(Kr + q * X3_KIMG + row * BA_RS + d4) = g[q];
+      split3(vreg[i], g[0], g[1], g[2]);
 #pragma unroll
       for (int q = 0; q < 3; ++q) {
         __bf16* T = Vt + q * X3_VIMG + d4 * BA_TS + row;
@@ -469,7 +459,7 @@ __global__ __launch_bounds__(256) void attn_x3_fwd_kernel(const float* __restric
       for (int r = 0; r < 16; ++r) s[r] = 0.f;
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
-        bf16x8_t ka[3];
+        bf16x8 ka[3];
 #pragma unroll
         for (int q = 0; q < 3; ++q) ka[q] = op_rows(Kr + q * X3_KIMG, sub, l31, half, t);
         s = mm6(ka, qf[t], s);                                                          // S^T[key][q], log2 domain
@@ -483,7 +473,7 @@ __global__ __launch_bounds__(256) void attn_x3_fwd_kernel(const float* __restric
       x3_softmax(s, o, m_run, l_run);
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
-        bf16x8_t pb[3], va[3];
+        bf16x8 pb[3], va[3];
         split_p8(s, t, pb);
 #pragma unroll
         for (int q = 0; q < 3; ++q) va[q] = op_cols(Vt + q * X3_VIMG, sub, l31, half, t);
@@ -508,7 +498,6 @@ __global__ __launch_bounds__(256) void attn_x3_fwd_kernel(const float* __restric
 // and the attention kernel moves a tile memory -> LDS with LDS-DMA (`buffer_load_dwordx4 ... lds`, 6 pieces per wave), double
 // buffered, and reads every operand with one conflict-free ds_read_b128.  Same split values, same instruction sequence per
 // accumulator: bitwise the results of attn_x3_fwd_kernel.
-typedef unsigned int au32x4 __attribute__((ext_vector_type(4)));
 constexpr int X3P_QB2_MIN_TOKENS = 2048;
 constexpr int X3P_TILE = 24 * 1024;           // bytes per 64-key tile: (4 K + 4 V^T fragments) x 3 planes x 1 KiB
 
@@ -532,11 +521,11 @@ __global__ __launch_bounds__(256) void attn_kv_split_kernel(const float* __restr
 #pragma unroll
       for (int j = 0; j < 8; ++j) v[j] = 0.f;
     }
-    bf16x8_t g[3];
+    bf16x8 g[3];
     split8(v, g);
     unsigned char* d = dst + (2 * sub + t) * 3072 + lane * 16;
 #pragma unroll
-    for (int q = 0; q < 3; ++q) *reinterpret_cast<bf16x8_t*>(d + q * 1024) = g[q];
+    for (int q = 0; q < 3; ++q) *reinterpret_cast<bf16x8*>(d + q * 1024) = g[q];
   }
   // V^T fragment (sub, t): this lane's d, 8 keys in accumulator order
   {
@@ -546,15 +535,15 @@ __global__ __launch_bounds__(256) void attn_kv_split_kernel(const float* __restr
       const int key = kt * BA_T + sub * 32 + 16 * t + 4 * half + (j & 3) + 8 * (j >> 2);
       v[j] = key < tokens ? base[2 * C + (long long)key * ld + l31] : 0.f;
     }
-    bf16x8_t g[3];
+    bf16x8 g[3];
     split8(v, g);
     unsigned char* d = dst + (4 + 2 * sub + t) * 3072 + lane * 16;
 #pragma unroll
-    for (int q = 0; q < 3; ++q) *reinterpret_cast<bf16x8_t*>(d + q * 1024) = g[q];
+    for (int q = 0; q < 3; ++q) *reinterpret_cast<bf16x8*>(d + q * 1024) = g[q];
   }
 }
 
-__device__ __forceinline__ void x3p_dma3(unsigned voff, const au32x4& rs, unsigned lds_dst) {     // 3 x 1 KiB, contiguous both sides
+__device__ __forceinline__ void x3p_dma3(unsigned voff, const u32x4& rs, unsigned lds_dst) {     // 3 x 1 KiB, contiguous both sides
   unsigned keep;
   asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"
                "buffer_load_dwordx4 %1, %2, 0 offen lds\n\t"
@@ -591,7 +580,7 @@ __global__ __launch_bounds__(256, 3) void attn_x3p_fwd_kernel(const float* __res
   const float* base = qkv + (long long)b * tokens * ld;
   const bool wave_active = q0 < tokens;
   constexpr float LOG2E = 1.4426950408889634f;
-  bf16x8_t qf[QB][2][3];
+  bf16x8 qf[QB][2][3];
   f32x16 o[QB];
   float m_run[QB], l_run[QB];
 #pragma unroll
@@ -613,14 +602,7 @@ __global__ __launch_bounds__(256, 3) void attn_x3p_fwd_kernel(const float* __res
   const int ntiles = (tokens + BA_T - 1) / BA_T;
   // this (sample, head)'s tiles as one buffer; wave w moves fragments 2w, 2w + 1 of a tile (6 KiB contiguous)
   const unsigned char* kvh = kv + ((long long)b * heads + h) * ntiles * X3P_TILE;
-  au32x4 rs;
-  {
-    const unsigned long long a = (unsigned long long)kvh;
-    rs.x = __builtin_amdgcn_readfirstlane((unsigned)a);
-    rs.y = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32) & 0xFFFFu);
-    rs.z = __builtin_amdgcn_readfirstlane((unsigned)ntiles * (unsigned)X3P_TILE);
-    rs.w = 0x00020000u;
-  }
+  const u32x4 rs = buffer_rsrc(kvh, (unsigned)ntiles * (unsigned)X3P_TILE);
   const unsigned lds0 = (unsigned)(size_t)smem_p;
   const unsigned woff = (unsigned)wave * 6144u + (unsigned)lane * 16u;
   auto fetch = [&](int kt) {                      // LDS-DMA of tile kt into buffer kt & 1 (tiles past the end: out of range, zeros)
@@ -647,11 +629,11 @@ __global__ __launch_bounds__(256, 3) void attn_x3p_fwd_kernel(const float* __res
         for (int r = 0; r < 16; ++r) s[j][r] = 0.f;
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
-        bf16x8_t ka[3];
+        bf16x8 ka[3];
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
           if constexpr (DBG & 16) { ka[q] = qf[0][t][q]; asm volatile("" : "+v"(ka[q])); }
-          else ka[q] = *reinterpret_cast<const bf16x8_t*>(tb + ((2 * sub + t) * 3 + q) * 1024);
+          else ka[q] = *reinterpret_cast<const bf16x8*>(tb + ((2 * sub + t) * 3 + q) * 1024);
         }
         if constexpr (DBG & 1) {
 #pragma unroll
@@ -682,29 +664,29 @@ __global__ __launch_bounds__(256, 3) void attn_x3p_fwd_kernel(const float* __res
       }
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
-        bf16x8_t va[3];
+        bf16x8 va[3];
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
           if constexpr (DBG & 16) { va[q] = qf[0][t][q]; asm volatile("" : "+v"(va[q])); }
-          else va[q] = *reinterpret_cast<const bf16x8_t*>(tb + ((4 + 2 * sub + t) * 3 + q) * 1024);
+          else va[q] = *reinterpret_cast<const bf16x8*>(tb + ((4 + 2 * sub + t) * 3 + q) * 1024);
         }
         if constexpr ((DBG & 12) != 0) {
 #pragma unroll
           for (int j = 0; j < QB; ++j) {
-            bf16x8_t pb[3];
+            bf16x8 pb[3];
             if constexpr (DBG & 4) {
 #pragma unroll
-              for (int q = 0; q < 3; ++q) pb[q] = __builtin_bit_cast(bf16x8_t, u32x4a{__float_as_uint(s[j][8 * t + q]), __float_as_uint(s[j][8 * t + q + 1]), __float_as_uint(s[j][8 * t + q + 2]), __float_as_uint(s[j][8 * t + q + 3])});
+              for (int q = 0; q < 3; ++q) pb[q] = __builtin_bit_cast(bf16x8, u32x4{__float_as_uint(s[j][8 * t + q]), __float_as_uint(s[j][8 * t + q + 1]), __float_as_uint(s[j][8 * t + q + 2]), __float_as_uint(s[j][8 * t + q + 3])});
             } else split_p8(s[j], t, pb);
             if constexpr (DBG & 8) asm volatile("" : "+v"(o[j]) : "v"(pb[0]), "v"(pb[1]), "v"(pb[2]), "v"(va[0]), "v"(va[1]), "v"(va[2]));
             else o[j] = mm6(va, pb, o[j]);
           }
         } else if constexpr (QB == 1) {
-          bf16x8_t pb[3];
+          bf16x8 pb[3];
           split_p8(s[0], t, pb);
           o[0] = mm6(va, pb, o[0]);                                                       // O^T[d][q] += V^T P^T
         } else {
-          bf16x8_t pb[2][3];
+          bf16x8 pb[2][3];
           split_p8(s[0], t, pb[0]);
           split_p8(s[1], t, pb[1]);
           o[0] = mm(va[2], pb[0][0], o[0]); o[1] = mm(va[2], pb[1][0], o[1]);
@@ -735,16 +717,16 @@ __global__ __launch_bounds__(256, 3) void attn_x3p_fwd_kernel(const float* __res
       if (q_valid) {
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-          bf16x4_t hh, mm_, ll;
+          bf16x4 hh, mm_, ll;
           // (the fp32 product is rounded BEFORE it is split -- no fused multiply-subtract into the residuals -- so the planes sum
           //  to exactly the value the fp32 output holds)
           float4 v4 = make_float4(mul_rounded(o[j][4 * g], inv), mul_rounded(o[j][4 * g + 1], inv), mul_rounded(o[j][4 * g + 2], inv), mul_rounded(o[j][4 * g + 3], inv));
           asm volatile("" : "+v"(v4.x), "+v"(v4.y), "+v"(v4.z), "+v"(v4.w));
-          split4(v4, hh, mm_, ll);
+          split3(v4, hh, mm_, ll);
           unsigned char* d = d0 + (g >> 1) * 3072 + (g & 1) * 512;
-          *reinterpret_cast<bf16x4_t*>(d) = hh;
-          *reinterpret_cast<bf16x4_t*>(d + 1024) = mm_;
-          *reinterpret_cast<bf16x4_t*>(d + 2048) = ll;
+          *reinterpret_cast<bf16x4*>(d) = hh;
+          *reinterpret_cast<bf16x4*>(d + 1024) = mm_;
+          *reinterpret_cast<bf16x4*>(d + 2048) = ll;
         }
       }
     }
@@ -768,7 +750,6 @@ __global__ __launch_bounds__(256, 3) void attn_x3p_fwd_kernel(const float* __res
 //   re-runs in the bf16x3 arithmetic; an element below 2^-9 keeps an ABSOLUTE precision of 2^-31), the probabilities by 2^14
 //   (the exponent argument is offset by 14).  Scores live in the domain scaled by 2^12; the output is rescaled at the end.
 // Tiles: per 64 keys 8 fragments x 2 planes of 1 KiB (16 KiB), same fragment order as the bf16x3 tiles above.
-typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
 constexpr int H2_TILE = 16 * 1024;
 constexpr float H2_S = 64.f;                  // 2^6: K, V, Q
 constexpr float H2_RANGE = 1000.f;            // |K|, |V|, |scale log2(e) Q| below this (x 64 < 65504, fp16's largest finite value)
@@ -788,22 +769,22 @@ __device__ __forceinline__ f32x2 widen_pk_f16(unsigned u) {
 }
 __device__ __forceinline__ unsigned split_lo_pk_f16(f32x2 p, unsigned h) { return h2_lo_pair(h, p.x, p.y); }      // (ldmk_common.h)
 // 8 (already scaled) values as their two fp16 images
-__device__ __forceinline__ void split8_h2(const float* v, f16x8_t (&o)[2]) {
-  u32x4a h, l;
+__device__ __forceinline__ void split8_h2(const float* v, f16x8 (&o)[2]) {
+  u32x4 h, l;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const f32x2 p = {v[2 * j], v[2 * j + 1]};
     h[j] = cvt_pk_f16(p);
     l[j] = split_lo_pk_f16(p, h[j]);
   }
-  o[0] = __builtin_bit_cast(f16x8_t, h);
-  o[1] = __builtin_bit_cast(f16x8_t, l);
+  o[0] = __builtin_bit_cast(f16x8, h);
+  o[1] = __builtin_bit_cast(f16x8, l);
 }
 __device__ __forceinline__ bool out_of_h2_range(float v) { return (__float_as_uint(v) & 0x7fffffffu) >= __float_as_uint(H2_RANGE); }   // (inf, NaN too)
-__device__ __forceinline__ f32x16 mmh(const f16x8_t a, const f16x8_t b, const f32x16 c) {
+__device__ __forceinline__ f32x16 mmh(const f16x8 a, const f16x8 b, const f32x16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
 }
-__device__ __forceinline__ f32x16 mmh3(const f16x8_t (&a)[2], const f16x8_t (&b)[2], f32x16 c) {
+__device__ __forceinline__ f32x16 mmh3(const f16x8 (&a)[2], const f16x8 (&b)[2], f32x16 c) {
   c = mmh(a[1], b[0], c);
   c = mmh(a[0], b[1], c);
   return mmh(a[0], b[0], c);
@@ -832,11 +813,11 @@ __global__ __launch_bounds__(256) void attn_kv_split_h2_kernel(const float* __re
     }
 #pragma unroll
     for (int j = 0; j < 8; ++j) { bad |= out_of_h2_range(v[j]); v[j] = h2_clamp(v[j]) * H2_S; }
-    f16x8_t g[2];
+    f16x8 g[2];
     split8_h2(v, g);
     unsigned char* d = dst + (2 * sub + t) * 2048 + lane * 16;
-    *reinterpret_cast<f16x8_t*>(d) = g[0];
-    *reinterpret_cast<f16x8_t*>(d + 1024) = g[1];
+    *reinterpret_cast<f16x8*>(d) = g[0];
+    *reinterpret_cast<f16x8*>(d + 1024) = g[1];
   }
   {
     float v[8];
@@ -847,16 +828,16 @@ __global__ __launch_bounds__(256) void attn_kv_split_h2_kernel(const float* __re
       bad |= out_of_h2_range(v[j]);
       v[j] = h2_clamp(v[j]) * H2_S;
     }
-    f16x8_t g[2];
+    f16x8 g[2];
     split8_h2(v, g);
     unsigned char* d = dst + (4 + 2 * sub + t) * 2048 + lane * 16;
-    *reinterpret_cast<f16x8_t*>(d) = g[0];
-    *reinterpret_cast<f16x8_t*>(d + 1024) = g[1];
+    *reinterpret_cast<f16x8*>(d) = g[0];
+    *reinterpret_cast<f16x8*>(d + 1024) = g[1];
   }
   if (bad) *range_flag = 1;
 }
 
-__device__ __forceinline__ void h2_dma4(unsigned voff, const au32x4& rs, unsigned lds_dst) {     // 4 x 1 KiB, contiguous both sides
+__device__ __forceinline__ void h2_dma4(unsigned voff, const u32x4& rs, unsigned lds_dst) {     // 4 x 1 KiB, contiguous both sides
   unsigned keep;
   asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"
                "buffer_load_dwordx4 %1, %2, 0 offen lds\n\t"
@@ -977,15 +958,15 @@ __device__ __forceinline__ void h2_lazy_raise(f32x16& s, f32x16& o, float& m_run
   }
 #define H2P_SUM(K) ps += f32x2{s[2 * (K)], s[2 * (K) + 1]};
 template <bool LOADK, bool LOADV, int OFF>
-__device__ __forceinline__ void h2p_step(f32x16& s, f32x16& sn, f32x16& op, f32x16& oc, float& m_run, float& l_run, const f16x8_t (&qn)[2][2],
-                                         f16x8_t (&kf)[2][2], f16x8_t (&vf)[2][2], f16x8_t (&pb)[2][2], const unsigned char* tk,
+__device__ __forceinline__ void h2p_step(f32x16& s, f32x16& sn, f32x16& op, f32x16& oc, float& m_run, float& l_run, const f16x8 (&qn)[2][2],
+                                         f16x8 (&kf)[2][2], f16x8 (&vf)[2][2], f16x8 (&pb)[2][2], const unsigned char* tk,
                                          const unsigned char* tv) {
   constexpr float INV = 1.0f / (H2_S * H2_S);
   if constexpr (LOADK) {                     // K of block b + 1 (its Q K^T starts at slice 6; the last reader of kf was the previous step)
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
-      for (int q = 0; q < 2; ++q) kf[t][q] = *reinterpret_cast<const f16x8_t*>(tk + (t * 2 + q) * 1024);
+      for (int q = 0; q < 2; ++q) kf[t][q] = *reinterpret_cast<const f16x8*>(tk + (t * 2 + q) * 1024);
   }
   H2P_FENCE();
   op = mmh(vf[0][1], pb[0][0], op);
@@ -1036,7 +1017,7 @@ __device__ __forceinline__ void h2p_step(f32x16& s, f32x16& sn, f32x16& op, f32x
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
-      for (int q = 0; q < 2; ++q) vf[t][q] = *reinterpret_cast<const f16x8_t*>(tv + (t * 2 + q) * 1024);
+      for (int q = 0; q < 2; ++q) vf[t][q] = *reinterpret_cast<const f16x8*>(tv + (t * 2 + q) * 1024);
   }
   {
     const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -1046,7 +1027,7 @@ __device__ __forceinline__ void h2p_step(f32x16& s, f32x16& sn, f32x16& op, f32x
   H2P_EXP2(6) H2P_EXP2(7)
   H2P_SUM(4) H2P_SUM(5)
   H2P_FENCE();
-  u32x4a h0, l0, h1, l1;
+  u32x4 h0, l0, h1, l1;
   sn = mmh(kf[0][0], qn[0][1], sn);
   H2P_FENCE();
   H2P_SPLIT_PAIR(h0, l0, 0, 0)
@@ -1079,24 +1060,24 @@ __device__ __forceinline__ void h2p_step(f32x16& s, f32x16& sn, f32x16& op, f32x
   H2P_FENCE();
   H2P_SPLIT_PAIR(h1, l1, 2, 6)
   H2P_SPLIT_PAIR(h1, l1, 3, 7)
-  pb[0][0] = __builtin_bit_cast(f16x8_t, h0);
-  pb[0][1] = __builtin_bit_cast(f16x8_t, l0);
-  pb[1][0] = __builtin_bit_cast(f16x8_t, h1);
-  pb[1][1] = __builtin_bit_cast(f16x8_t, l1);
+  pb[0][0] = __builtin_bit_cast(f16x8, h0);
+  pb[0][1] = __builtin_bit_cast(f16x8, l0);
+  pb[1][0] = __builtin_bit_cast(f16x8, h1);
+  pb[1][1] = __builtin_bit_cast(f16x8, l1);
   H2P_FENCE();
 }
 
 // The same step with the lazy running maximum (above)
 template <bool LOADK, bool LOADV, int OFF>
-__device__ __forceinline__ void h2p_step_lazy(f32x16& s, f32x16& sn, f32x16& op, f32x16& oc, float& m_run, float& l_run, const f16x8_t (&qn)[2][2],
-                                              f16x8_t (&kf)[2][2], f16x8_t (&vf)[2][2], f16x8_t (&pb)[2][2], const unsigned char* tk,
+__device__ __forceinline__ void h2p_step_lazy(f32x16& s, f32x16& sn, f32x16& op, f32x16& oc, float& m_run, float& l_run, const f16x8 (&qn)[2][2],
+                                              f16x8 (&kf)[2][2], f16x8 (&vf)[2][2], f16x8 (&pb)[2][2], const unsigned char* tk,
                                               const unsigned char* tv, bool& bad) {
   constexpr float INV = 1.0f / (H2_S * H2_S);
   if constexpr (LOADK) {
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
-      for (int q = 0; q < 2; ++q) kf[t][q] = *reinterpret_cast<const f16x8_t*>(tk + (t * 2 + q) * 1024);
+      for (int q = 0; q < 2; ++q) kf[t][q] = *reinterpret_cast<const f16x8*>(tk + (t * 2 + q) * 1024);
   }
   const float c = (float)OFF - m_run;
   const f32x2 inv2 = {INV, INV}, off2 = {c, c};
@@ -1142,14 +1123,14 @@ __device__ __forceinline__ void h2p_step_lazy(f32x16& s, f32x16& sn, f32x16& op,
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
-      for (int q = 0; q < 2; ++q) vf[t][q] = *reinterpret_cast<const f16x8_t*>(tv + (t * 2 + q) * 1024);
+      for (int q = 0; q < 2; ++q) vf[t][q] = *reinterpret_cast<const f16x8*>(tv + (t * 2 + q) * 1024);
   }
   {
     const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     sn = mmh(kf[0][1], qn[0][0], zero);
   }
   H2P_FENCE();
-  u32x4a h0, l0, h1, l1;
+  u32x4 h0, l0, h1, l1;
   H2P_SPLIT_PAIR(h0, l0, 0, 0)
   H2P_SPLIT_PAIR(h0, l0, 1, 1)
   H2P_FENCE();
@@ -1173,10 +1154,10 @@ __device__ __forceinline__ void h2p_step_lazy(f32x16& s, f32x16& sn, f32x16& op,
   sn = mmh(kf[1][0], qn[1][0], sn);
   H2P_FENCE();
   H2P_SPLIT_PAIR(h1, l1, 3, 7)
-  pb[0][0] = __builtin_bit_cast(f16x8_t, h0);
-  pb[0][1] = __builtin_bit_cast(f16x8_t, l0);
-  pb[1][0] = __builtin_bit_cast(f16x8_t, h1);
-  pb[1][1] = __builtin_bit_cast(f16x8_t, l1);
+  pb[0][0] = __builtin_bit_cast(f16x8, h0);
+  pb[0][1] = __builtin_bit_cast(f16x8, l0);
+  pb[1][0] = __builtin_bit_cast(f16x8, h1);
+  pb[1][1] = __builtin_bit_cast(f16x8, l1);
   H2P_FENCE();
 }
 
@@ -1208,7 +1189,7 @@ __global__ __launch_bounds__(256) void attn_h2_fwd_kernel(const float* __restric
   const float* base = qkv + (long long)b * tokens * ld;
   const bool wave_active = q0 < tokens;
   constexpr float LOG2E = 1.4426950408889634f;
-  f16x8_t qf[QB][2][2];
+  f16x8 qf[QB][2][2];
   f32x16 o[QB];
   float m_run[QB], l_run[QB];
   bool bad = false;
@@ -1233,14 +1214,7 @@ __global__ __launch_bounds__(256) void attn_h2_fwd_kernel(const float* __restric
   if (bad) *range_flag = 1;
   const int ntiles = (tokens + BA_T - 1) / BA_T;
   const unsigned char* kvh = kv + ((long long)b * heads + h) * ntiles * H2_TILE;
-  au32x4 rs;
-  {
-    const unsigned long long a = (unsigned long long)kvh;
-    rs.x = __builtin_amdgcn_readfirstlane((unsigned)a);
-    rs.y = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32) & 0xFFFFu);
-    rs.z = __builtin_amdgcn_readfirstlane((unsigned)ntiles * (unsigned)H2_TILE);
-    rs.w = 0x00020000u;
-  }
+  const u32x4 rs = buffer_rsrc(kvh, (unsigned)ntiles * (unsigned)H2_TILE);
   const unsigned lds0 = (unsigned)(size_t)smem_h;
   const unsigned woff = (unsigned)wave * 4096u + (unsigned)lane * 16u;
   auto fetch = [&](int kt) {                      // LDS-DMA of tile kt into buffer kt & 1 (tiles past the end: out of range, zeros)
@@ -1252,7 +1226,7 @@ __global__ __launch_bounds__(256) void attn_h2_fwd_kernel(const float* __restric
     // have landed before the last step of tile kt (its Q K^T reads K of tile kt + 1): the fetch of tile kt + 2 is issued there,
     // behind the barrier that also says every wave has read the last fragment of tile kt -- two buffers, as before.
     f32x16 sa, sb;
-    f16x8_t kf[2][2], vf[2][2], pb[2][2];
+    f16x8 kf[2][2], vf[2][2], pb[2][2];
     const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     fetch(0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1264,8 +1238,8 @@ __global__ __launch_bounds__(256) void attn_h2_fwd_kernel(const float* __restric
       for (int t = 0; t < 2; ++t)
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
-          kf[t][q] = *reinterpret_cast<const f16x8_t*>(tb + (t * 2 + q) * 1024);
-          vf[t][q] = __builtin_bit_cast(f16x8_t, u32x4a{0u, 0u, 0u, 0u});        // (the first step's P V: zeros times zeros onto zeros)
+          kf[t][q] = *reinterpret_cast<const f16x8*>(tb + (t * 2 + q) * 1024);
+          vf[t][q] = __builtin_bit_cast(f16x8, u32x4{0u, 0u, 0u, 0u});        // (the first step's P V: zeros times zeros onto zeros)
           pb[t][q] = vf[t][q];
         }
       sa = mmh3(kf[0], qf[0][0], zero);
@@ -1321,9 +1295,9 @@ __global__ __launch_bounds__(256) void attn_h2_fwd_kernel(const float* __restric
         for (int r = 0; r < 16; ++r) s[j][r] = 0.f;
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
-        f16x8_t ka[2];
+        f16x8 ka[2];
 #pragma unroll
-        for (int q = 0; q < 2; ++q) ka[q] = *reinterpret_cast<const f16x8_t*>(tb + ((2 * sub + t) * 2 + q) * 1024);
+        for (int q = 0; q < 2; ++q) ka[q] = *reinterpret_cast<const f16x8*>(tb + ((2 * sub + t) * 2 + q) * 1024);
 #pragma unroll
         for (int j = 0; j < QB; ++j) s[j] = mmh3(ka, qf[j][t], s[j]);                      // 2^12 S^T[key][q], log2 domain
       }
@@ -1339,15 +1313,15 @@ __global__ __launch_bounds__(256) void attn_h2_fwd_kernel(const float* __restric
       for (int j = 0; j < QB; ++j) h2_softmax(s[j], o[j], m_run[j], l_run[j]);
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
-        f16x8_t va[2];
+        f16x8 va[2];
 #pragma unroll
-        for (int q = 0; q < 2; ++q) va[q] = *reinterpret_cast<const f16x8_t*>(tb + ((4 + 2 * sub + t) * 2 + q) * 1024);
+        for (int q = 0; q < 2; ++q) va[q] = *reinterpret_cast<const f16x8*>(tb + ((4 + 2 * sub + t) * 2 + q) * 1024);
 #pragma unroll
         for (int j = 0; j < QB; ++j) {
           float pv[8];
 #pragma unroll
           for (int i = 0; i < 8; ++i) pv[i] = s[j][8 * t + i];
-          f16x8_t pb[2];
+          f16x8 pb[2];
           split8_h2(pv, pb);
           o[j] = mmh3(va, pb, o[j]);                                                       // 2^20 O^T[d][q] += V^T P^T
         }
@@ -1373,8 +1347,7 @@ __global__ __launch_bounds__(256) void attn_h2_fwd_kernel(const float* __restric
         for (int g = 0; g < 4; ++g) {
           float v[4] = {mul_rounded(o[j][4 * g], mul), mul_rounded(o[j][4 * g + 1], mul), mul_rounded(o[j][4 * g + 2], mul), mul_rounded(o[j][4 * g + 3], mul)};
           asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]));
-          typedef _Float16 f16x4_t __attribute__((ext_vector_type(4)));
-          f16x4_t hh, ll;
+          f16x4 hh, ll;
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             bad2 |= out_of_h2_range(v[e]);
@@ -1383,8 +1356,8 @@ __global__ __launch_bounds__(256) void attn_h2_fwd_kernel(const float* __restric
             ll[e] = (_Float16)(sv - (float)hh[e]);
           }
           unsigned char* d = d0 + (g >> 1) * 2048 + (g & 1) * 512;
-          *reinterpret_cast<f16x4_t*>(d) = hh;
-          *reinterpret_cast<f16x4_t*>(d + 1024) = ll;
+          *reinterpret_cast<f16x4*>(d) = hh;
+          *reinterpret_cast<f16x4*>(d + 1024) = ll;
         }
         if (bad2) *range_flag = 1;
       }

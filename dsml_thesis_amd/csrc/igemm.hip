@@ -21,8 +21,9 @@
 //     are bitwise reproducible.  That is what keeps 256 CUs busy on the low-resolution layers
 //     (M = 64 rows per sample at 8x8, K up to 9*1280).
 #include "ldmk_common.h"
+#include "ldmk_split.h"
+#include "ldmk_epilogue.h"
 #include <stdlib.h>
-#include <type_traits>
 
 // Diagnostic build only (tools/igemm_probe.hip defines LDMK_IG_STAMPS): per-wave cycle totals of the main loop's phases
 // (barrier 1, LDS store, barrier 2, global-load issue, MFMA block) go to args.splitk_ws (split-K off in the probe) as [wave][8] 64-bit ticks.
@@ -35,45 +36,6 @@
 #endif
 
 namespace ldmk {
-
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ bf16x4 to_bf16x4(const float4& v) {          // round-to-nearest-even (v_cvt_pk_bf16_f32)
-  return bf16x4{(__bf16)v.x, (__bf16)v.y, (__bf16)v.z, (__bf16)v.w};
-}
-
-// LDMK_COMPUTE_F16X2: x' = 2^6 x = hi + lo, hi = fp16(x'), lo = fp16(x' - hi) (round-to-nearest-even; x' - hi exact in fp32)
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-constexpr float H2_A_SCALE = 64.f;            // 2^LDMK_F16X2_A_EXP
-__device__ __forceinline__ void split2h(const float4& v, f16x4& h, f16x4& l) {     // v already scaled; lo: h2_lo_pair (ldmk_common.h)
-  h = f16x4{(_Float16)v.x, (_Float16)v.y, (_Float16)v.z, (_Float16)v.w};
-  typedef unsigned u32x2h __attribute__((ext_vector_type(2)));
-  const u32x2h hu = __builtin_bit_cast(u32x2h, h);
-  l = __builtin_bit_cast(f16x4, u32x2h{h2_lo_pair(hu.x, v.x, v.y), h2_lo_pair(hu.y, v.z, v.w)});
-}
-__device__ __forceinline__ bool h2_out_of_range(const float4& v) {                 // |x| >= LDMK_F16X2_RANGE, inf or NaN
-  constexpr unsigned LIM = 0x447a0000u;       // 1000.0f
-  return (__float_as_uint(v.x) & 0x7fffffffu) >= LIM || (__float_as_uint(v.y) & 0x7fffffffu) >= LIM ||
-         (__float_as_uint(v.z) & 0x7fffffffu) >= LIM || (__float_as_uint(v.w) & 0x7fffffffu) >= LIM;
-}
-
-template <int I, int N, class F>
-__device__ __forceinline__ void ig_static_for(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    ig_static_for<I + 1, N>(f);
-  }
-}
-
-// exact three-way split x = hi + mid + lo (each difference below is exact in fp32: the subtrahend is the leading part of x)
-__device__ __forceinline__ float bf_up(__bf16 b) { return (float)b; }
-__device__ __forceinline__ void split3(const float4& v, bf16x4& h, bf16x4& m, bf16x4& l) {
-  h = to_bf16x4(v);
-  const float4 r = make_float4(v.x - bf_up(h[0]), v.y - bf_up(h[1]), v.z - bf_up(h[2]), v.w - bf_up(h[3]));
-  m = to_bf16x4(r);
-  l = to_bf16x4(make_float4(r.x - bf_up(m[0]), r.y - bf_up(m[1]), r.z - bf_up(m[2]), r.w - bf_up(m[3])));
-}
 
 // BF = true: bf16 matrix-core compute for the training step (BASELINE configs[4]).  Operands stay fp32 in HBM; they are
 // rounded to bf16 (RNE) while being staged, after the fp32 prologue (LayerNorm / GroupNorm-affine), into K-contiguous LDS
@@ -90,25 +52,7 @@ __device__ __forceinline__ void split3(const float4& v, bf16x4& h, bf16x4& m, bf
 // statistics pass, ldmk_ln_stats_split) -- rows mode, one source, no staging prologue.  Its staging is then a 16-byte copy like
 // B's: no split arithmetic per N-tile (a GEGLU projection re-split every A element N/BN = 8..40 times), 6 + 8 loads and
 // LDS stores per thread and slice instead of 4 + 8 loads, ~90 vector operations and 12 + 8 stores.
-// The lean form of the epilogue below (one wave tile wholly inside M x N, no split-K, no folded LayerNorm, no
-// GEGLU, 32-row tiles inside one sample): no per-element row predicate and operand branches -- in the general form every
-// residual load sits in its own basic block and waits for itself -- and the operand set is a template argument: 1 = per-sample
-// vector, 2 = residual, 3 = neither, 4 = both.  Same arithmetic, rounding by rounding (csrc/igemm_ps.hip has the same pair of forms).
-__device__ __forceinline__ float ig_col_finish(float acc_alpha, float bias) {
-#pragma clang fp contract(off)
-  return acc_alpha + bias;
-}
-__device__ __forceinline__ float ig_col_finish(float acc_alpha, float bias, float extra) {
-#pragma clang fp contract(off)
-  const float t = acc_alpha + bias;
-  return t + extra;
-}
-__device__ __forceinline__ float ig_col_finish(float acc_alpha, float bias, float vec, float res) {
-#pragma clang fp contract(off)
-  float t = acc_alpha + bias;
-  t = t + vec;
-  return t + res;
-}
+// the lean form of this kernel's epilogue (col_lean of csrc/ldmk_epilogue.h, kept as this kernel's own copy: see the epilogue)
 template <int TM, int TN, int LEAN>
 __device__ __forceinline__ void ig_lean_epilogue(const ldmk_igemm_args& p, f32x16 (&acc)[TM][TN], const int rowbase, const int colbase, const int bz,
                                                  const int l31, const int half) {
@@ -133,10 +77,10 @@ __device__ __forceinline__ void ig_lean_epilogue(const ldmk_igemm_args& p, f32x1
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const float t = acc[i][j][r] * alpha;
-        if constexpr (LEAN == 3) vals[r] = ig_col_finish(t, bv);
-        else if constexpr (LEAN == 1) vals[r] = ig_col_finish(t, bv, vec);
-        else if constexpr (LEAN == 2) vals[r] = ig_col_finish(t, bv, extra[r]);
-        else vals[r] = ig_col_finish(t, bv, vec, extra[r]);
+        if constexpr (LEAN == 3) vals[r] = col_finish(t, bv);
+        else if constexpr (LEAN == 1) vals[r] = col_finish(t, bv, vec);
+        else if constexpr (LEAN == 2) vals[r] = col_finish(t, bv, extra[r]);
+        else vals[r] = col_finish(t, bv, vec, extra[r]);
         outp[obase + (unsigned)(((r & 3) + 8 * (r >> 2)) * p.ldc)] = vals[r];
       }
       if (p.stats_out) {
@@ -264,11 +208,10 @@ __global__ __launch_bounds__(256) void igemm_kernel(const ldmk_igemm_args p, con
     }
   }
 
-  typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
   float4 areg[NS][AROWS];
   float4 breg[X3 ? 1 : NS][X3 ? 1 : BROWS];
-  u32x4_t bxreg[NS][BSI];               // X3: the next slice's pre-split weight items
-  u32x4_t axreg[NS][ASI];               // ASP: ... and pre-split activation items
+  u32x4 bxreg[NS][BSI];               // X3: the next slice's pre-split weight items
+  u32x4 axreg[NS][ASI];               // ASP: ... and pre-split activation items
 
   // ---- fast gather (every launch except the upsampling convolutions).  Measured with s_memtime stamps
   // (tools/igemm_probe.hip) on the ResBlock convolutions: of 7400 cycles per 32-deep slice the generic gather below spent
@@ -351,7 +294,7 @@ __global__ __launch_bounds__(256) void igemm_kernel(const ldmk_igemm_args p, con
     }
   }
   auto bload = [&](__amdgpu_buffer_rsrc_t rs, unsigned off) -> float4 {
-    const u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)off, 0, 0);
+    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)off, 0, 0);
     return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
   };
   auto load_slices_fast = [&](int it) {
@@ -508,12 +451,12 @@ __global__ __launch_bounds__(256) void igemm_kernel(const ldmk_igemm_args p, con
 #pragma unroll
         for (int i = 0; i < ASI; ++i) {
           if (tid + 256 * i < 3 * BM * 4)
-            *reinterpret_cast<u32x4_t*>(reinterpret_cast<char*>(As16) + axlds[i] + j * 64) = axreg[j][i];
+            *reinterpret_cast<u32x4*>(reinterpret_cast<char*>(As16) + axlds[i] + j * 64) = axreg[j][i];
         }
 #pragma unroll
         for (int i = 0; i < BSI; ++i) {
           if (tid + 256 * i < NI * BN * 4)
-            *reinterpret_cast<u32x4_t*>(reinterpret_cast<char*>(Bx16) + bxlds[i] + j * 64) = bxreg[j][i];
+            *reinterpret_cast<u32x4*>(reinterpret_cast<char*>(Bx16) + bxlds[i] + j * 64) = bxreg[j][i];
         }
         continue;
       }
@@ -525,7 +468,7 @@ __global__ __launch_bounds__(256) void igemm_kernel(const ldmk_igemm_args p, con
 #pragma unroll
         for (int i = 0; i < BSI; ++i) {                 // B first: its loads were issued first (see load_slices_fast)
           if (tid + 256 * i < NI * BN * 4)
-            *reinterpret_cast<u32x4_t*>(reinterpret_cast<char*>(Bx16) + bxlds[i] + j * 64) = bxreg[j][i];
+            *reinterpret_cast<u32x4*>(reinterpret_cast<char*>(Bx16) + bxlds[i] + j * 64) = bxreg[j][i];
         }
 #pragma unroll
         for (int i = 0; i < AROWS; ++i) {
@@ -544,7 +487,7 @@ __global__ __launch_bounds__(256) void igemm_kernel(const ldmk_igemm_args p, con
               v = h2_clamp4(v);
             }
             f16x4 h, l;
-            split2h(make_float4(v.x * H2_A_SCALE, v.y * H2_A_SCALE, v.z * H2_A_SCALE, v.w * H2_A_SCALE), h, l);
+            split2h(scaled(v, H2_SCALE), h, l);
             *reinterpret_cast<f16x4*>(d) = h;
             *reinterpret_cast<f16x4*>(d + AIMG) = l;
           } else {
@@ -623,7 +566,7 @@ __global__ __launch_bounds__(256) void igemm_kernel(const ldmk_igemm_args p, con
       fa(0, 0);
       fb(0, 0);
       __builtin_amdgcn_sched_group_barrier(0x100, NI * TM + NI, 0);       // (the first step's own reads: they open the sequence)
-      ig_static_for<0, NSTEP>([&](auto tc) {
+      static_for<0, NSTEP>([&](auto tc) {
         constexpr int t = decltype(tc)::value;
         constexpr int s = t / TN, j = t - s * TN;
         constexpr bool more = t + 1 < NSTEP, newk = more && (t + 1) % TN == 0;
@@ -804,7 +747,10 @@ __global__ __launch_bounds__(256) void igemm_kernel(const ldmk_igemm_args p, con
   if constexpr (H2) {
     if (h2_bad) *p.range_flag = 1;
   }
-  // ---- epilogue.  C/D map: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
+  // ---- epilogue.  igemm_kernel keeps its OWN copy of the lane = column forms that igemm_ws.hip and igemm_ps.hip take from
+  // csrc/ldmk_epilogue.h (same statements; the finishers col_finish are the shared ones): with the shared pieces inlined here the
+  // compiler's SGPR spill counts of most instantiations moved by 1..4, and this kernel's register budget is a condition.
+  // C/D map: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
   const int rowbase = m0 + wm * (32 * TM);
   const int colbase = n0 + wn * (32 * TN);
   if (splitk > 1) {   // raw partial slab [ks][M][N]
@@ -1276,77 +1222,39 @@ static void plan(const ldmk_igemm_args& a, int* cfg_out, int* splitk_out, long l
   *splitk_out = best_sk;
 }
 
-// bf16 matrix-core compute (args.compute = LDMK_COMPUTE_BF16): the WK = 1 tile shapes
-template <bool BT>
-static int dispatch_bf16(const ldmk_igemm_args& a, int cfg, int splitk, float* ws, hipStream_t st) {
+// The 16-bit matrix-core forms (BF != 0) are built for WK = 1: one switch over their four tile shapes.
+//   BF = 1  bf16 compute, fp32 weights as they lie (args.compute = LDMK_COMPUTE_BF16); the gather is chosen at run time (FG_RT)
+//   BF = 2  bf16 compute with the weights pre-packed (args.w_split = one bf16 image, ldmk_pack_wbf16t): the training step's forward GEMMs
+//   BF = 3  fp32-accurate three-way bf16 split (LDMK_COMPUTE_BF16X3), pre-split weights; ASP: the A operand pre-split as well
+//           (ldmk_ln_stats_split): copies only
+//   BF = 4  fp32-accurate two-way fp16 split (LDMK_COMPUTE_F16X2): three matrix instructions per product
+// BF >= 2 read their weights through the fast gather only (static_assert in igemm_kernel): FG pinned.
+template <int TM, int TN, int WM, int WN, int KS, bool BT, int BF, bool ASP, bool FG_RT>
+static int launch_wk1(const ldmk_igemm_args& a, int splitk, float* ws, hipStream_t st) {
+  if constexpr (FG_RT) return launch_cfg<TM, TN, WM, WN, 1, KS, false, BT, BF>(a, splitk, ws, st);
+  else return launch_cfg_g<TM, TN, WM, WN, 1, KS, false, BT, BF, true, ASP>(a, splitk, ws, st);
+}
+template <bool BT, int BF, bool ASP, bool FG_RT>
+static int dispatch_wk1(const ldmk_igemm_args& a, int cfg, int splitk, float* ws, hipStream_t st) {
   const bool geglu = a.epi == LDMK_EPI_GEGLU;
   if (cfg == 3) cfg = 4;                       // 64x64 with K split over the waves -> 64x64, 64 k per stage
   if (cfg == 6) cfg = geglu ? 2 : 5;           // 64x160 with K split over wave pairs -> 128x160
   if (geglu && !kCfg[cfg - 1].even_tn) cfg = 1;
   switch (cfg) {
-    case 1: return launch_cfg<2, 2, 2, 2, 1, 1, false, BT, 1>(a, splitk, ws, st);
-    case 2: return launch_cfg<1, 2, 2, 2, 1, 2, false, BT, 1>(a, splitk, ws, st);
-    case 4: return launch_cfg<1, 1, 2, 2, 1, 2, false, BT, 1>(a, splitk, ws, st);
-    default: return launch_cfg<1, 5, 4, 1, 1, 1, false, BT, 1>(a, splitk, ws, st);
-  }
-}
-
-// fp32-accurate three-way bf16 split (args.compute = LDMK_COMPUTE_BF16X3): the WK = 1 tile shapes, pre-split weights
-static int dispatch_x3(const ldmk_igemm_args& a, int cfg, int splitk, float* ws, hipStream_t st) {
-  const bool geglu = a.epi == LDMK_EPI_GEGLU;
-  if (cfg == 3) cfg = 4;
-  if (cfg == 6) cfg = geglu ? 2 : 5;
-  if (geglu && !kCfg[cfg - 1].even_tn) cfg = 1;
-  if (a.a_split) {                             // the A operand pre-split as well (ldmk_ln_stats_split): copies only
-    switch (cfg) {
-      case 1: return launch_cfg_g<2, 2, 2, 2, 1, 1, false, false, 3, true, true>(a, splitk, ws, st);
-      case 2: return launch_cfg_g<1, 2, 2, 2, 1, 2, false, false, 3, true, true>(a, splitk, ws, st);
-      case 4: return launch_cfg_g<1, 1, 2, 2, 1, 2, false, false, 3, true, true>(a, splitk, ws, st);
-      default: return launch_cfg_g<1, 5, 4, 1, 1, 1, false, false, 3, true, true>(a, splitk, ws, st);
-    }
-  }
-  switch (cfg) {
-    case 1: return launch_cfg_g<2, 2, 2, 2, 1, 1, false, false, 3, true>(a, splitk, ws, st);
-    case 2: return launch_cfg_g<1, 2, 2, 2, 1, 2, false, false, 3, true>(a, splitk, ws, st);
-    case 4: return launch_cfg_g<1, 1, 2, 2, 1, 2, false, false, 3, true>(a, splitk, ws, st);
-    default: return launch_cfg_g<1, 5, 4, 1, 1, 1, false, false, 3, true>(a, splitk, ws, st);
-  }
-}
-
-// fp32-accurate two-way fp16 split (args.compute = LDMK_COMPUTE_F16X2): the same tile shapes, three matrix instructions per product
-static int dispatch_h2(const ldmk_igemm_args& a, int cfg, int splitk, float* ws, hipStream_t st) {
-  const bool geglu = a.epi == LDMK_EPI_GEGLU;
-  if (cfg == 3) cfg = 4;
-  if (cfg == 6) cfg = geglu ? 2 : 5;
-  if (geglu && !kCfg[cfg - 1].even_tn) cfg = 1;
-  switch (cfg) {
-    case 1: return launch_cfg_g<2, 2, 2, 2, 1, 1, false, false, 4, true>(a, splitk, ws, st);
-    case 2: return launch_cfg_g<1, 2, 2, 2, 1, 2, false, false, 4, true>(a, splitk, ws, st);
-    case 4: return launch_cfg_g<1, 1, 2, 2, 1, 2, false, false, 4, true>(a, splitk, ws, st);
-    default: return launch_cfg_g<1, 5, 4, 1, 1, 1, false, false, 4, true>(a, splitk, ws, st);
-  }
-}
-
-// bf16 compute with the weights pre-packed (args.w_split = one bf16 image, ldmk_pack_wbf16t): the training step's forward GEMMs
-static int dispatch_bf16_packed(const ldmk_igemm_args& a, int cfg, int splitk, float* ws, hipStream_t st) {
-  const bool geglu = a.epi == LDMK_EPI_GEGLU;
-  if (cfg == 3) cfg = 4;
-  if (cfg == 6) cfg = geglu ? 2 : 5;
-  if (geglu && !kCfg[cfg - 1].even_tn) cfg = 1;
-  switch (cfg) {
-    case 1: return launch_cfg_g<2, 2, 2, 2, 1, 1, false, false, 2, true>(a, splitk, ws, st);
-    case 2: return launch_cfg_g<1, 2, 2, 2, 1, 2, false, false, 2, true>(a, splitk, ws, st);
-    case 4: return launch_cfg_g<1, 1, 2, 2, 1, 2, false, false, 2, true>(a, splitk, ws, st);
-    default: return launch_cfg_g<1, 5, 4, 1, 1, 1, false, false, 2, true>(a, splitk, ws, st);
+    case 1: return launch_wk1<2, 2, 2, 2, 1, BT, BF, ASP, FG_RT>(a, splitk, ws, st);
+    case 2: return launch_wk1<1, 2, 2, 2, 2, BT, BF, ASP, FG_RT>(a, splitk, ws, st);
+    case 4: return launch_wk1<1, 1, 2, 2, 2, BT, BF, ASP, FG_RT>(a, splitk, ws, st);
+    default: return launch_wk1<1, 5, 4, 1, 1, BT, BF, ASP, FG_RT>(a, splitk, ws, st);
   }
 }
 
 template <bool BT>
 static int dispatch(const ldmk_igemm_args& a, int cfg, int splitk, float* ws, hipStream_t st) {
-  if (a.compute == LDMK_COMPUTE_BF16 && a.w_split && !BT && igemm_fast_gather_ok(a)) return dispatch_bf16_packed(a, cfg, splitk, ws, st);
-  if (a.compute == LDMK_COMPUTE_BF16) return dispatch_bf16<BT>(a, cfg, splitk, ws, st);
-  if (a.compute == LDMK_COMPUTE_BF16X3) return dispatch_x3(a, cfg, splitk, ws, st);
-  if (a.compute == LDMK_COMPUTE_F16X2) return dispatch_h2(a, cfg, splitk, ws, st);
+  if (a.compute == LDMK_COMPUTE_BF16 && a.w_split && !BT && igemm_fast_gather_ok(a)) return dispatch_wk1<false, 2, false, false>(a, cfg, splitk, ws, st);
+  if (a.compute == LDMK_COMPUTE_BF16) return dispatch_wk1<BT, 1, false, true>(a, cfg, splitk, ws, st);
+  if (a.compute == LDMK_COMPUTE_BF16X3)
+    return a.a_split ? dispatch_wk1<false, 3, true, false>(a, cfg, splitk, ws, st) : dispatch_wk1<false, 3, false, false>(a, cfg, splitk, ws, st);
+  if (a.compute == LDMK_COMPUTE_F16X2) return dispatch_wk1<false, 4, false, false>(a, cfg, splitk, ws, st);
   if (a.epi == LDMK_EPI_GEGLU && !kCfg[cfg - 1].even_tn) cfg = 3;   // GEGLU needs (value, gate) tile pairs
   switch (cfg) {
     case 1: return launch_cfg<2, 2, 2, 2, 1, 1, false, BT>(a, splitk, ws, st);   // 128x128

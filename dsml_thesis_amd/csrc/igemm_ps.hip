@@ -23,13 +23,11 @@
 // row, registers = 4 x 4 consecutive columns), which stores float4 rows and can write the result pre-split in the PS layout
 // for the next GEMM (args.out_ps) -- each activation element is then split exactly once, by its producer.
 #include "ldmk_common.h"
+#include "ldmk_split.h"
+#include "ldmk_epilogue.h"
 #include <stdlib.h>
 
 namespace ldmk {
-
-typedef __bf16 pbf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 pbf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int pu32x4 __attribute__((ext_vector_type(4)));
 
 // What-if probes (drop the DMA / the matrix instructions / the epilogue, phase stamps, phase stagger: results are garbage with them)
 // exist only in builds made with -DLDMK_PS_PROBES (tools/ps_probe.sh, tools/pw_stamps.py); the shipped library ignores LDMK_PS_DEBUG /
@@ -39,28 +37,22 @@ constexpr bool PS_PROBES = true;
 #else
 constexpr bool PS_PROBES = false;
 #endif
-static int ps_probe_bits() {
+static int ps_probe_bits() {      // LDMK_PS_DEBUG | LDMK_PS_STAGGER << 8, read once; always 0 in the shipped build
   if (!PS_PROBES) return 0;
-  const int dbg = ps_probe_bits();
+  static const int dbg = [] {
+    const char* d = getenv("LDMK_PS_DEBUG");
+    const char* s = getenv("LDMK_PS_STAGGER");
+    return (d ? atoi(d) : 0) | ((s ? atoi(s) : 0) << 8);
+  }();
   return dbg;
 }
 
 constexpr unsigned PS_OOB = 0x80000000u;      // a byte offset beyond every buffer here (< 2 GiB each): reads as zeros, no memory traffic
 
-__device__ __forceinline__ pu32x4 ps_rsrc(const void* ptr, unsigned bytes) {      // raw buffer descriptor, uniform -> SGPRs
-  const unsigned long long a = (unsigned long long)ptr;
-  pu32x4 r;
-  r.x = __builtin_amdgcn_readfirstlane((unsigned)a);
-  r.y = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32) & 0xFFFFu);
-  r.z = __builtin_amdgcn_readfirstlane(bytes);
-  r.w = 0x00020000u;
-  return r;
-}
-
 // One unit = the three planes of one 32-row block at one k-slab: 3 KiB contiguous in memory and in the LDS stage.
 // LDS destination = M0 + instruction offset + 16 lane; memory address = base + voff + instruction offset (probed on gfx950:
 // tools/probe/dma_probe.hip); M0 is saved / restored around the group (the compiler owns it outside the statement).
-__device__ __forceinline__ void ps_dma3(unsigned voff, const pu32x4& rs, unsigned lds_dst) {
+__device__ __forceinline__ void ps_dma3(unsigned voff, const u32x4& rs, unsigned lds_dst) {
   unsigned keep;
   asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"
                "buffer_load_dwordx4 %1, %2, 0 offen lds\n\t"
@@ -73,7 +65,7 @@ __device__ __forceinline__ void ps_dma3(unsigned voff, const pu32x4& rs, unsigne
 // PL = planes per operand: 3 (bf16x3: hi, mid, lo bf16) or 2 (F16X2: hi, lo fp16 of the operand scaled into fp16's range; the
 // same layout with 2-KiB units).  One unit = the PL planes of one 32-row block at one k-slab.
 template <int PL>
-__device__ __forceinline__ void ps_dma(unsigned voff, const pu32x4& rs, unsigned lds_dst) {
+__device__ __forceinline__ void ps_dma(unsigned voff, const u32x4& rs, unsigned lds_dst) {
   if constexpr (PL == 3) {
     ps_dma3(voff, rs, lds_dst);
   } else {
@@ -84,36 +76,6 @@ __device__ __forceinline__ void ps_dma(unsigned voff, const pu32x4& rs, unsigned
                  "s_mov_b32 m0, %0"
                  : "=&s"(keep) : "v"(voff), "s"(rs), "s"(lds_dst) : "memory");
   }
-}
-
-typedef _Float16 pf16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 pf16x8 __attribute__((ext_vector_type(8)));
-constexpr float PS_H2_SCALE = 64.f;            // 2^LDMK_F16X2_A_EXP
-__device__ __forceinline__ void ps_split2h(const float4& v, pf16x4& h, pf16x4& l) {       // v already scaled; the split of igemm.hip's split2h
-  h = pf16x4{(_Float16)v.x, (_Float16)v.y, (_Float16)v.z, (_Float16)v.w};
-  typedef unsigned pu32x2 __attribute__((ext_vector_type(2)));
-  const pu32x2 hu = __builtin_bit_cast(pu32x2, h);
-  l = __builtin_bit_cast(pf16x4, pu32x2{h2_lo_pair(hu.x, v.x, v.y), h2_lo_pair(hu.y, v.z, v.w)});
-}
-__device__ __forceinline__ bool ps_h2_out_of_range(const float4& v) {                       // |x| >= LDMK_F16X2_RANGE, inf or NaN
-  constexpr unsigned LIM = 0x447a0000u;
-  return (__float_as_uint(v.x) & 0x7fffffffu) >= LIM || (__float_as_uint(v.y) & 0x7fffffffu) >= LIM ||
-         (__float_as_uint(v.z) & 0x7fffffffu) >= LIM || (__float_as_uint(v.w) & 0x7fffffffu) >= LIM;
-}
-// (activations, s = 2^6: saturated just inside the range -- h2_clamp, ldmk_common.h; weights, any s: their exponent is chosen at pack time)
-__device__ __forceinline__ float4 ps_scaled(const float4& v, float s) { return make_float4(v.x * s, v.y * s, v.z * s, v.w * s); }
-__device__ __forceinline__ float4 ps_scaled_sat(const float4& v) {
-  return make_float4(h2_clamp(v.x) * PS_H2_SCALE, h2_clamp(v.y) * PS_H2_SCALE, h2_clamp(v.z) * PS_H2_SCALE, h2_clamp(v.w) * PS_H2_SCALE);
-}
-
-template <int N> __device__ __forceinline__ void ps_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" :: "i"(N) : "memory"); }
-
-__device__ __forceinline__ pbf16x4 ps_bf4(const float4& v) { return pbf16x4{(__bf16)v.x, (__bf16)v.y, (__bf16)v.z, (__bf16)v.w}; }
-__device__ __forceinline__ void ps_split3(const float4& v, pbf16x4& h, pbf16x4& m, pbf16x4& l) {      // exact: h + m + l == v
-  h = ps_bf4(v);
-  const float4 r = make_float4(v.x - (float)h[0], v.y - (float)h[1], v.z - (float)h[2], v.w - (float)h[3]);
-  m = ps_bf4(r);
-  l = ps_bf4(make_float4(r.x - (float)m[0], r.y - (float)m[1], r.z - (float)m[2], r.w - (float)m[3]));
 }
 
 // Zeros for the optional epilogue operands: a NULL bias / column sum / per-sample vector / residual reads these instead, so the
@@ -128,48 +90,14 @@ __device__ __attribute__((aligned(16))) const float kPsZeros[4] = {0.f, 0.f, 0.f
 // half-lanes, one v_permlane32_swap per register pairs them up.  A V^T fragment wants lane = d: one pass through a per-wave LDS
 // scratch (`kv_ts`, 32 x 33 floats; the ring is free by then).
 constexpr int PS_KV_TILE = 16 * 1024;          // = H2_TILE of csrc/attention_bf16.hip
-// the folded LayerNorm of one accumulator value + bias: rstd (acc - mean colsum) + b with the roundings of igemm.hip / rgemm.hip --
-// one fma, one multiply, one add.  Contraction is switched off here: in the general epilogue a select sits between the multiply
-// and the add, in the lean one nothing does, and the compiler would fuse them into a second fma (one rounding less: other bits).
-__device__ __forceinline__ float ps_lnf_bias(float acc, float mean, float cs, float rstd, float bias) {
-#pragma clang fp contract(off)
-  const float t = __builtin_fmaf(-mean, cs, acc) * rstd;
-  return t + bias;
-}
-// the same for a launch without a folded LayerNorm: alpha acc + b (+ 0 for the absent per-sample vector) + residual, each its own
-// rounding as in the general epilogue (where the `if (lnf)` select sits between the multiply and the first add)
-__device__ __forceinline__ float ps_bias_res(float acc_alpha, float bias, float vec, float res) {
-#pragma clang fp contract(off)
-  float t = acc_alpha + bias;
-  t = t + vec;                 // (the per-sample vector, or +0 where the general form adds its zero)
-  return t + res;
-}
-// lane = column form: alpha acc + bias [+ per-sample vector | + residual], each addition its own rounding as in the general form
-__device__ __forceinline__ float ps_col_finish(float acc_alpha, float bias) {
-#pragma clang fp contract(off)
-  return acc_alpha + bias;
-}
-__device__ __forceinline__ float ps_col_finish(float acc_alpha, float bias, float extra) {
-#pragma clang fp contract(off)
-  const float t = acc_alpha + bias;
-  return t + extra;
-}
-__device__ __forceinline__ float ps_col_finish(float acc_alpha, float bias, float vec, float res) {
-#pragma clang fp contract(off)
-  float t = acc_alpha + bias;
-  t = t + vec;
-  return t + res;
-}
-// LEAN != 0 (transposed form; chosen per wave when the whole wave tile is inside M x N, no split-K, no per-sample vector): no row /
-// column predicates, no loads of absent operands, no select around the LayerNorm arithmetic -- the operand set is a template
-// argument: 1 = folded LayerNorm, no residual (the GEGLU and QKV projections), 2 = residual, no LayerNorm (attn.to_out, ff.net.2),
-// 3 = neither (Winograd planes, upsampling phases), 4 = residual + per-sample vector (attn1.to_out carrying the single-token
-// cross-attention vector).  Lane = column form (the convolutions: bias, then the time-embedding vector
-// or the skip connection, GroupNorm records): 1 = per-sample vector, 2 = residual, 3 = neither, 4 = both -- there every element of the
-// general form sits behind its own row predicate and operand branches, so each residual load waited for itself (577 s_waitcnt in
-// the 160 -> 160 convolution's kernel); the lean form asks for the 16 residuals of a tile at once.  Same arithmetic, rounding by
-// rounding, as the general form (0).  The GEGLU
-// epilogue was ~3000 vector instructions per wave for 64 outputs per lane, a third of them addressing and predication.
+// LEAN != 0 (chosen per wave when the whole wave tile is inside M x N, no split-K): no row / column predicates, no loads of absent
+// operands, no select around the LayerNorm arithmetic -- the operand set is a template argument.  Transposed form (no per-sample
+// vector unless a residual comes with it): 1 = folded LayerNorm, no residual (the GEGLU and QKV projections), 2 = residual, no
+// LayerNorm (attn.to_out, ff.net.2), 3 = neither (Winograd planes, upsampling phases), 4 = residual + per-sample vector
+// (attn1.to_out carrying the single-token cross-attention vector).  The GEGLU epilogue was ~3000 vector instructions per wave for
+// 64 outputs per lane, a third of them addressing and predication.  Lane = column form (the convolutions: bias, then the
+// time-embedding vector or the skip connection, GroupNorm records): col_lean of csrc/ldmk_epilogue.h.  Same arithmetic, rounding
+// by rounding, as the general form (0).
 template <int TM, int TN, bool TR, int PL = 3, bool KV = false, int LEAN = 0>
 __device__ __forceinline__ void ps_epilogue(const ldmk_igemm_args& p, f32x16 (&acc)[TM][TN], const int rowbase, const int colbase,
                                             const int splitk, const int ks, const int bz, float* __restrict__ ws, const int lane,
@@ -259,9 +187,9 @@ __device__ __forceinline__ void ps_epilogue(const ldmk_igemm_args& p, f32x16 (&a
             float4 v = make_float4(acc[i][jt][4 * q] * alpha, acc[i][jt][4 * q + 1] * alpha, acc[i][jt][4 * q + 2] * alpha,
                                    acc[i][jt][4 * q + 3] * alpha);
             if constexpr (L_LNF) {
-              v.x = ps_lnf_bias(v.x, mean, cs[q].x, rstd, bi[q].x); v.y = ps_lnf_bias(v.y, mean, cs[q].y, rstd, bi[q].y);
-              v.z = ps_lnf_bias(v.z, mean, cs[q].z, rstd, bi[q].z); v.w = ps_lnf_bias(v.w, mean, cs[q].w, rstd, bi[q].w);
-            } else if constexpr (L_ANY) {        // (bias, +0, residual: in ps_bias_res below, once the GEGLU gate is through)
+              v.x = lnf_bias(v.x, mean, cs[q].x, rstd, bi[q].x); v.y = lnf_bias(v.y, mean, cs[q].y, rstd, bi[q].y);
+              v.z = lnf_bias(v.z, mean, cs[q].z, rstd, bi[q].z); v.w = lnf_bias(v.w, mean, cs[q].w, rstd, bi[q].w);
+            } else if constexpr (L_ANY) {        // (bias, +0, residual: in bias_res below, once the GEGLU gate is through)
             } else {
               if (lnf) {      // same arithmetic as igemm.hip / rgemm.hip / igemm_reduce_kernel
                 v.x = fmaf(-mean, cs[q].x, v.x) * rstd; v.y = fmaf(-mean, cs[q].y, v.y) * rstd;
@@ -276,8 +204,8 @@ __device__ __forceinline__ void ps_epilogue(const ldmk_igemm_args& p, f32x16 (&a
                 float4 g = make_float4(acc[i][jg][4 * q] * alpha, acc[i][jg][4 * q + 1] * alpha, acc[i][jg][4 * q + 2] * alpha,
                                        acc[i][jg][4 * q + 3] * alpha);
                 if constexpr (L_LNF) {
-                  g.x = ps_lnf_bias(g.x, mean, csg[q].x, rstd, big[q].x); g.y = ps_lnf_bias(g.y, mean, csg[q].y, rstd, big[q].y);
-                  g.z = ps_lnf_bias(g.z, mean, csg[q].z, rstd, big[q].z); g.w = ps_lnf_bias(g.w, mean, csg[q].w, rstd, big[q].w);
+                  g.x = lnf_bias(g.x, mean, csg[q].x, rstd, big[q].x); g.y = lnf_bias(g.y, mean, csg[q].y, rstd, big[q].y);
+                  g.z = lnf_bias(g.z, mean, csg[q].z, rstd, big[q].z); g.w = lnf_bias(g.w, mean, csg[q].w, rstd, big[q].w);
                 } else {
                   if (lnf) {
                     g.x = fmaf(-mean, csg[q].x, g.x) * rstd; g.y = fmaf(-mean, csg[q].y, g.y) * rstd;
@@ -292,8 +220,8 @@ __device__ __forceinline__ void ps_epilogue(const ldmk_igemm_args& p, f32x16 (&a
               v.x += 0.f; v.y += 0.f; v.z += 0.f; v.w += 0.f;
             } else if constexpr (L_ANY) {
               const float4 r4 = L_RS ? rs[q] : make_float4(0.f, 0.f, 0.f, 0.f), b4 = L_BV ? bv[q] : make_float4(0.f, 0.f, 0.f, 0.f);
-              v.x = ps_bias_res(v.x, bi[q].x, b4.x, r4.x); v.y = ps_bias_res(v.y, bi[q].y, b4.y, r4.y);
-              v.z = ps_bias_res(v.z, bi[q].z, b4.z, r4.z); v.w = ps_bias_res(v.w, bi[q].w, b4.w, r4.w);
+              v.x = bias_res(v.x, bi[q].x, b4.x, r4.x); v.y = bias_res(v.y, bi[q].y, b4.y, r4.y);
+              v.z = bias_res(v.z, bi[q].z, b4.z, r4.z); v.w = bias_res(v.w, bi[q].w, b4.w, r4.w);
             } else {
               v.x += bv[q].x; v.y += bv[q].y; v.z += bv[q].z; v.w += bv[q].w;
               v.x += rs[q].x; v.y += rs[q].y; v.z += rs[q].z; v.w += rs[q].w;
@@ -307,17 +235,17 @@ __device__ __forceinline__ void ps_epilogue(const ldmk_igemm_args& p, f32x16 (&a
               if (ops_) {
                 unsigned char* d = ops_ + psrow + (long long)((otile >> 4) + (q >> 1)) * (PL * 1024) + (q & 1) * 512;
                 if constexpr (PL == 3) {
-                  pbf16x4 h, m, l;
-                  ps_split3(v, h, m, l);
-                  *reinterpret_cast<pbf16x4*>(d) = h;
-                  *reinterpret_cast<pbf16x4*>(d + 1024) = m;
-                  *reinterpret_cast<pbf16x4*>(d + 2048) = l;
+                  bf16x4 h, m, l;
+                  split3(v, h, m, l);
+                  *reinterpret_cast<bf16x4*>(d) = h;
+                  *reinterpret_cast<bf16x4*>(d + 1024) = m;
+                  *reinterpret_cast<bf16x4*>(d + 2048) = l;
                 } else {
-                  bad_ps |= ps_h2_out_of_range(v);
-                  pf16x4 h, l;
-                  ps_split2h(ps_scaled_sat(v), h, l);
-                  *reinterpret_cast<pf16x4*>(d) = h;
-                  *reinterpret_cast<pf16x4*>(d + 1024) = l;
+                  bad_ps |= h2_out_of_range(v);
+                  f16x4 h, l;
+                  split2h(scaled_sat(v), h, l);
+                  *reinterpret_cast<f16x4*>(d) = h;
+                  *reinterpret_cast<f16x4*>(d + 1024) = l;
                 }
               }
             }
@@ -346,13 +274,13 @@ __device__ __forceinline__ void ps_epilogue(const ldmk_igemm_args& p, f32x16 (&a
                     vals[4 + e] = __uint_as_float(r[1]);
                   }
                   const float4 v0 = make_float4(vals[0], vals[1], vals[2], vals[3]), v1 = make_float4(vals[4], vals[5], vals[6], vals[7]);
-                  bad |= ps_h2_out_of_range(v0) || ps_h2_out_of_range(v1);
-                  pf16x4 h0, l0, h1, l1;
-                  ps_split2h(ps_scaled_sat(v0), h0, l0);
-                  ps_split2h(ps_scaled_sat(v1), h1, l1);
+                  bad |= h2_out_of_range(v0) || h2_out_of_range(v1);
+                  f16x4 h0, l0, h1, l1;
+                  split2h(scaled_sat(v0), h0, l0);
+                  split2h(scaled_sat(v1), h1, l1);
                   unsigned char* d = dst + (2 * sub + t) * 2048;
-                  *reinterpret_cast<pf16x8*>(d) = pf16x8{h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
-                  *reinterpret_cast<pf16x8*>(d + 1024) = pf16x8{l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
+                  *reinterpret_cast<f16x8*>(d) = f16x8{h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
+                  *reinterpret_cast<f16x8*>(d + 1024) = f16x8{l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
                 }
               } else {
                 // V^T: [token = l31][d = 8 q + 4 half + e] -> LDS -> lane = d reads 8 keys in the order the probabilities leave
@@ -369,13 +297,13 @@ __device__ __forceinline__ void ps_epilogue(const ldmk_igemm_args& p, f32x16 (&a
 #pragma unroll
                   for (int jx = 0; jx < 8; ++jx) vals[jx] = kv_ts[(16 * t + 4 * half + (jx & 3) + 8 * (jx >> 2)) * 33 + l31];
                   const float4 v0 = make_float4(vals[0], vals[1], vals[2], vals[3]), v1 = make_float4(vals[4], vals[5], vals[6], vals[7]);
-                  bad |= ps_h2_out_of_range(v0) || ps_h2_out_of_range(v1);
-                  pf16x4 h0, l0, h1, l1;
-                  ps_split2h(ps_scaled_sat(v0), h0, l0);
-                  ps_split2h(ps_scaled_sat(v1), h1, l1);
+                  bad |= h2_out_of_range(v0) || h2_out_of_range(v1);
+                  f16x4 h0, l0, h1, l1;
+                  split2h(scaled_sat(v0), h0, l0);
+                  split2h(scaled_sat(v1), h1, l1);
                   unsigned char* d = dst + (4 + 2 * sub + t) * 2048;
-                  *reinterpret_cast<pf16x8*>(d) = pf16x8{h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
-                  *reinterpret_cast<pf16x8*>(d + 1024) = pf16x8{l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
+                  *reinterpret_cast<f16x8*>(d) = f16x8{h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
+                  *reinterpret_cast<f16x8*>(d + 1024) = f16x8{l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
                 }
                 __builtin_amdgcn_s_waitcnt(0xC07F);
                 __builtin_amdgcn_wave_barrier();
@@ -389,178 +317,32 @@ __device__ __forceinline__ void ps_epilogue(const ldmk_igemm_args& p, f32x16 (&a
     if (bad_ps) *p.range_flag = 1;
     return;
   } else {
-    // ---- epilogue, lane = column (igemm_ws.hip's).  C/D map: col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
-    if (splitk > 1) {   // raw partial slab [ks][M][N]; igemm_reduce_kernel (or the consumer, raw_slabs) sums them
-      float* slab = ws + ((long long)bz * splitk + ks) * p.M * p.N;
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        const int col = colbase + j * 32 + l31;
-        if (col >= p.N) continue;
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int row = rowbase + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-            if (row < p.M) slab[(long long)row * p.N + col] = acc[i][j][r];
-          }
-      }
+    // ---- lane = column: the shared forms of csrc/ldmk_epilogue.h (igemm_kernel's and igemm_ws_kernel's)
+    if (splitk > 1) {   // igemm_reduce_kernel (or the consumer, raw_slabs) sums the slabs
+      col_slab_store<TM, TN>(p, acc, rowbase, colbase, bz, l31, half, splitk, ks, ws);
       return;
     }
-    float* __restrict__ outp = p.out + (long long)bz * p.out_bstride;
-    const float* resp = p.residual ? p.residual + (long long)bz * p.out_bstride : nullptr;
     if (p.epi == LDMK_EPI_GEGLU) {
-      if constexpr (TN % 2 == 0) {
-#pragma unroll
-        for (int j = 0; j < TN; j += 2) {
-          const int cv = colbase + j * 32 + l31;        // packed value column
-          const int cg = cv + 32;                       // packed gate column
-          if (cv >= p.N) continue;
-          const int oc = ((colbase + j * 32) >> 1) + l31;
-          const float bv = p.bias ? p.bias[cv] : 0.f, bg = p.bias ? p.bias[cg] : 0.f;
-          const float csv = lnf ? p.ln_colsum[cv] : 0.f, csg = lnf ? p.ln_colsum[cg] : 0.f;
-#pragma unroll
-          for (int i = 0; i < TM; ++i) {
-            float2 st[16];
-            if (lnf) {
-#pragma unroll
-              for (int r = 0; r < 16; ++r) st[r] = stats2[min(rowbase + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half, p.M - 1)];
-            }
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-              const int row = rowbase + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-              if (row < p.M) {
-                float v = acc[i][j][r] * alpha, g = acc[i][j + 1][r] * alpha;
-                if (lnf) {
-                  v = fmaf(-st[r].x, csv, v) * st[r].y;
-                  g = fmaf(-st[r].x, csg, g) * st[r].y;
-                }
-                v += bv;
-                g += bg;
-                outp[(long long)row * p.ldc + oc] = v * gelu_erf_f(g);
-              }
-            }
-          }
-        }
-      }
+      col_geglu<TM, TN>(p, acc, rowbase, colbase, bz, l31, half, lnf);
       return;
     }
-    if constexpr (LEAN != 0) {
-      // (dispatch: whole wave tile inside M x N, no split-K, no folded LayerNorm, 32-row tiles inside one sample)
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        const int col = colbase + j * 32 + l31;
-        const float bv = p.bias ? p.bias[col] : 0.f;
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-          const int r0 = rowbase + i * 32 + 4 * half;
-          const unsigned obase = (unsigned)r0 * (unsigned)p.ldc + (unsigned)col;
-          float extra[16], vec = 0.f;
-          if constexpr (LEAN == 1 || LEAN == 4) vec = p.batch_vec[(long long)((rowbase + i * 32) / p.rows_per_sample) * p.batch_vec_ld + col];
-          if constexpr (LEAN == 2 || LEAN == 4) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) extra[r] = resp[obase + (unsigned)(((r & 3) + 8 * (r >> 2)) * p.ldc)];
-          }
-          float vals[16];
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const float t = acc[i][j][r] * alpha;
-            if constexpr (LEAN == 3) vals[r] = ps_col_finish(t, bv);
-            else if constexpr (LEAN == 1) vals[r] = ps_col_finish(t, bv, vec);
-            else if constexpr (LEAN == 2) vals[r] = ps_col_finish(t, bv, extra[r]);
-            else vals[r] = ps_col_finish(t, bv, vec, extra[r]);
-            outp[obase + (unsigned)(((r & 3) + 8 * (r >> 2)) * p.ldc)] = vals[r];
-          }
-          if (p.stats_out) {
-            const float shift = __shfl(vals[0], l31, 64);      // row 0 of the tile
-            float sm = 0.f, sq = 0.f;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-              const float d = vals[r] - shift;
-              sm += d;
-              sq = fmaf(d, d, sq);
-            }
-            sm += __shfl_xor(sm, 32, 64);
-            sq += __shfl_xor(sq, 32, 64);
-            if (half == 0) {
-              float* d = p.stats_out + ((long long)((rowbase + i * 32) >> 5) * p.N + col) * 3;
-              d[0] = shift; d[1] = sm; d[2] = sq;
-            }
-          }
-        }
-      }
-      return;
-    }
-    const bool tile_in_sample = p.rows_per_sample % 32 == 0;
-    int smp[TM];
-#pragma unroll
-    for (int i = 0; i < TM; ++i) smp[i] = p.batch_vec ? min(rowbase + i * 32, p.M - 1) / p.rows_per_sample : 0;
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      const int col = colbase + j * 32 + l31;
-      if (col >= p.N) continue;
-      const float bv = p.bias ? p.bias[col] : 0.f;
-      const float cs = lnf ? p.ln_colsum[col] : 0.f;
-#pragma unroll
-      for (int i = 0; i < TM; ++i) {
-        float vals[16];
-        const int r0 = rowbase + i * 32 + 4 * half;
-        if (lnf) {
-          float2 st[16];
-#pragma unroll
-          for (int r = 0; r < 16; ++r) st[r] = stats2[min(r0 + (r & 3) + 8 * (r >> 2), p.M - 1)];
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc[i][j][r] = fmaf(-st[r].x, cs, acc[i][j][r] * alpha) * st[r].y;
-        }
-        const unsigned obase = (unsigned)r0 * (unsigned)p.ldc + (unsigned)col;
-        const float vec = (p.batch_vec && tile_in_sample) ? p.batch_vec[(long long)smp[i] * p.batch_vec_ld + col] : 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int dr = (r & 3) + 8 * (r >> 2);
-          float v = 0.f;
-          if (r0 + dr < p.M) {
-            v = (lnf ? acc[i][j][r] : acc[i][j][r] * alpha) + bv;
-            if (p.batch_vec) v += tile_in_sample ? vec : p.batch_vec[(long long)((r0 + dr) / p.rows_per_sample) * p.batch_vec_ld + col];
-            const unsigned o = obase + (unsigned)(dr * p.ldc);
-            if (resp) v += resp[o];
-            outp[o] = v;
-          }
-          vals[r] = v;
-        }
-        if (p.stats_out && rowbase + i * 32 < p.M) {
-          // GroupNorm partial record of this 32-row tile x column (the record of gn_partial_kernel / igemm_kernel)
-          const float shift = __shfl(vals[0], l31, 64);      // row 0 of the tile
-          float sm = 0.f, sq = 0.f;
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const float d = vals[r] - shift;
-            sm += d;
-            sq = fmaf(d, d, sq);
-          }
-          sm += __shfl_xor(sm, 32, 64);
-          sq += __shfl_xor(sq, 32, 64);
-          if (half == 0) {
-            float* d = p.stats_out + ((long long)((rowbase + i * 32) >> 5) * p.N + col) * 3;
-            d[0] = shift; d[1] = sm; d[2] = sq;
-          }
-        }
-      }
-    }
+    // (dispatch, col_lean_form: whole wave tile inside M x N, no split-K, no folded LayerNorm, 32-row tiles inside one sample)
+    if constexpr (LEAN != 0) col_lean<TM, TN, LEAN>(p, acc, rowbase, colbase, bz, l31, half);
+    else col_general<TM, TN>(p, acc, rowbase, colbase, bz, l31, half, lnf);
   }
 }
 
 // which lean epilogue (ps_epilogue's LEAN) a wave tile ending at (row_end, col_end) may take; 0 = the general one
 template <bool TR>
 __device__ __forceinline__ int ps_lean_form(const ldmk_igemm_args& p, const int splitk, const bool off, const int row_end, const int col_end) {
-  if (off || splitk != 1 || row_end > p.M || col_end > p.N) return 0;
-  const bool lf = p.a_tf == LDMK_TF_LAYERNORM_FOLDED, geglu = p.epi == LDMK_EPI_GEGLU;
-  if (p.batch_vec && p.rows_per_sample % 32 != 0) return 0;      // (a 32-row tile inside one sample)
-  if constexpr (TR) {
-    if (lf) return p.residual || p.batch_vec ? 0 : 1;
-    if (geglu || (p.batch_vec && !p.residual)) return 0;
-    return p.batch_vec ? 4 : (p.residual ? 2 : 3);
+  if constexpr (!TR) {
+    return col_lean_form(p, splitk, off, row_end, col_end);
   } else {
-    if (lf || geglu) return 0;
-    return p.batch_vec ? (p.residual ? 4 : 1) : (p.residual ? 2 : 3);
+    if (off || splitk != 1 || row_end > p.M || col_end > p.N) return 0;
+    if (p.batch_vec && p.rows_per_sample % 32 != 0) return 0;      // (a 32-row tile inside one sample)
+    if (p.a_tf == LDMK_TF_LAYERNORM_FOLDED) return p.residual || p.batch_vec ? 0 : 1;
+    if (p.epi == LDMK_EPI_GEGLU || (p.batch_vec && !p.residual)) return 0;
+    return p.batch_vec ? 4 : (p.residual ? 2 : 3);
   }
 }
 
@@ -600,8 +382,8 @@ __global__ __launch_bounds__(64 * NWM * NWN, 2) void igemm_ps_kernel(const ldmk_
 
   // (dbg, probe runs only -- LDMK_PS_DEBUG: bit 0 = zero-record descriptors: every DMA is issued but dropped by the range check,
   //  no memory traffic; bit 1 = no DMA instructions at all; bit 2 = no matrix instructions.  Results are garbage then.)
-  const pu32x4 rs_a = ps_rsrc(reinterpret_cast<const unsigned char*>(p.a_ps) + (long long)bz * p.a_ps_bstride, (dbg & 1) ? 0u : (unsigned)Mb * (unsigned)Kb * (unsigned)UB);
-  const pu32x4 rs_b = ps_rsrc(reinterpret_cast<const unsigned char*>(p.w_ps) + (long long)bz * p.w_ps_bstride, (dbg & 1) ? 0u : (unsigned)Nb * (unsigned)Kb * (unsigned)UB);
+  const u32x4 rs_a = buffer_rsrc(reinterpret_cast<const unsigned char*>(p.a_ps) + (long long)bz * p.a_ps_bstride, (dbg & 1) ? 0u : (unsigned)Mb * (unsigned)Kb * (unsigned)UB);
+  const u32x4 rs_b = buffer_rsrc(reinterpret_cast<const unsigned char*>(p.w_ps) + (long long)bz * p.w_ps_bstride, (dbg & 1) ? 0u : (unsigned)Nb * (unsigned)Kb * (unsigned)UB);
   // this wave's units u = wave + NW i: byte offset of the block's first k-slab (wave-uniform), or PS_OOB for blocks past the edge
   unsigned ubase[UHI];
 #pragma unroll
@@ -652,20 +434,20 @@ __global__ __launch_bounds__(64 * NWM * NWN, 2) void igemm_ps_kernel(const ldmk_
   for (int it = 0; it < n16; ++it) {
     // stage `it` of THIS wave has landed when all but the (NS - 2) younger stages' loads are done; the barrier then makes
     // every wave's part visible and certifies that buffer (it - 1) % NS is no longer read
-    if (hi_wave) ps_wait_vm<PL * UHI * (NS - 2)>(); else ps_wait_vm<PL * ULO * (NS - 2)>();
+    if (hi_wave) wait_vm<PL * UHI * (NS - 2)>(); else wait_vm<PL * ULO * (NS - 2)>();
     asm volatile("s_barrier" ::: "memory");
     issue(it + NS - 1);
     const unsigned char* sb = smem_ps + (it % NS) * STAGE + lane16;
-    pbf16x8 a8[PL][TM];
+    bf16x8 a8[PL][TM];
 #pragma unroll
     for (int g = 0; g < PL; ++g)
 #pragma unroll
-      for (int i = 0; i < TM; ++i) a8[g][i] = *reinterpret_cast<const pbf16x8*>(sb + ((wm * TM + i) * PL + g) * 1024);
+      for (int i = 0; i < TM; ++i) a8[g][i] = *reinterpret_cast<const bf16x8*>(sb + ((wm * TM + i) * PL + g) * 1024);
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
-      pbf16x8 b8[PL];
+      bf16x8 b8[PL];
 #pragma unroll
-      for (int g = 0; g < PL; ++g) b8[g] = *reinterpret_cast<const pbf16x8*>(sb + ((FA + wn * TN + j) * PL + g) * 1024);
+      for (int g = 0; g < PL; ++g) b8[g] = *reinterpret_cast<const bf16x8*>(sb + ((FA + wn * TN + j) * PL + g) * 1024);
       if (dbg & 4) {
 #pragma unroll
         for (int i = 0; i < TM; ++i)
@@ -677,8 +459,8 @@ __global__ __launch_bounds__(64 * NWM * NWN, 2) void igemm_ps_kernel(const ldmk_
       for (int i = 0; i < TM; ++i) {
         if constexpr (PL == 2) {
           // F16X2: lo hi, hi lo, hi hi (planes: 0 = hi, 1 = lo) -- the order of igemm_kernel<BF = 4>
-          const pf16x8 ah = __builtin_bit_cast(pf16x8, a8[0][i]), al = __builtin_bit_cast(pf16x8, a8[1][i]);
-          const pf16x8 bh = __builtin_bit_cast(pf16x8, b8[0]), bl = __builtin_bit_cast(pf16x8, b8[1]);
+          const f16x8 ah = __builtin_bit_cast(f16x8, a8[0][i]), al = __builtin_bit_cast(f16x8, a8[1][i]);
+          const f16x8 bh = __builtin_bit_cast(f16x8, b8[0]), bl = __builtin_bit_cast(f16x8, b8[1]);
           if constexpr (TR) {
             acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh, al, acc[i][j], 0, 0, 0);
             acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bl, ah, acc[i][j], 0, 0, 0);
@@ -706,7 +488,7 @@ __global__ __launch_bounds__(64 * NWM * NWN, 2) void igemm_ps_kernel(const ldmk_
       }
     }
   }
-  ps_wait_vm<0>();             // (the trailing out-of-range loads still target this workgroup's LDS)
+  wait_vm<0>();             // (the trailing out-of-range loads still target this workgroup's LDS)
   if (dbg & 16) {              // probe: no epilogue (one never-taken store keeps the accumulators live)
     float keep = 0.f;
 #pragma unroll
@@ -781,8 +563,8 @@ __global__ __launch_bounds__(512) void igemm_pw_kernel(const ldmk_igemm_args p, 
     const int pw = wave - 4;
     const int Kb = p.K / 16;
     const int Mb = (p.M + 31) / 32, Nb = p.N / 32;
-    const pu32x4 rs_a = ps_rsrc(reinterpret_cast<const unsigned char*>(p.a_ps) + (long long)bz * p.a_ps_bstride, (dbg & 1) ? 0u : (unsigned)Mb * (unsigned)Kb * 3072u);
-    const pu32x4 rs_b = ps_rsrc(reinterpret_cast<const unsigned char*>(p.w_ps) + (long long)bz * p.w_ps_bstride, (dbg & 1) ? 0u : (unsigned)Nb * (unsigned)Kb * 3072u);
+    const u32x4 rs_a = buffer_rsrc(reinterpret_cast<const unsigned char*>(p.a_ps) + (long long)bz * p.a_ps_bstride, (dbg & 1) ? 0u : (unsigned)Mb * (unsigned)Kb * 3072u);
+    const u32x4 rs_b = buffer_rsrc(reinterpret_cast<const unsigned char*>(p.w_ps) + (long long)bz * p.w_ps_bstride, (dbg & 1) ? 0u : (unsigned)Nb * (unsigned)Kb * 3072u);
     unsigned ubase[UHI];
 #pragma unroll
     for (int i = 0; i < UHI; ++i) {
@@ -812,19 +594,19 @@ __global__ __launch_bounds__(512) void igemm_pw_kernel(const ldmk_igemm_args p, 
 #pragma unroll
     for (int s = 0; s < NS - 1; ++s) issue(s);
     PW_T(0);
-    if (hi_wave) ps_wait_vm<3 * UHI * (NS - 2)>(); else ps_wait_vm<3 * ULO * (NS - 2)>();      // stage 0
+    if (hi_wave) wait_vm<3 * UHI * (NS - 2)>(); else wait_vm<3 * ULO * (NS - 2)>();      // stage 0
     PW_T(1);
     asm volatile("s_barrier" ::: "memory");
     PW_T(2);
     for (int it = 0; it < n16; ++it) {
-      if (hi_wave) ps_wait_vm<3 * UHI * (NS - 3)>(); else ps_wait_vm<3 * ULO * (NS - 3)>();    // stage it + 1
+      if (hi_wave) wait_vm<3 * UHI * (NS - 3)>(); else wait_vm<3 * ULO * (NS - 3)>();    // stage it + 1
       PW_T(1);
       asm volatile("s_barrier" ::: "memory");
       PW_T(2);
       issue(it + NS - 1);
       PW_T(0);
     }
-    ps_wait_vm<0>();
+    wait_vm<0>();
     if ((dbg & 8) && lane == 0 && p.splitk_counters) {
       unsigned long long* d = reinterpret_cast<unsigned long long*>(p.splitk_counters) + ((long long)blockIdx.x * 8 + wave) * 4;
       d[0] = t_acc[0]; d[1] = t_acc[1]; d[2] = t_acc[2]; d[3] = __builtin_amdgcn_s_memtime() - t_begin;
@@ -844,16 +626,16 @@ __global__ __launch_bounds__(512) void igemm_pw_kernel(const ldmk_igemm_args p, 
 
   const unsigned char* abase = smem_ps + wm * TM * 3072 + lane16;
   const unsigned char* bbase = smem_ps + FA * 3072 + lane16;
-  pbf16x8 A2[2][3][TM], B2[2][3];
-  auto ldA = [&](pbf16x8 (&a)[3][TM], int buf) {
+  bf16x8 A2[2][3][TM], B2[2][3];
+  auto ldA = [&](bf16x8 (&a)[3][TM], int buf) {
 #pragma unroll
     for (int g = 0; g < 3; ++g)
 #pragma unroll
-      for (int i = 0; i < TM; ++i) a[g][i] = *reinterpret_cast<const pbf16x8*>(abase + buf * STAGE + (i * 3 + g) * 1024);
+      for (int i = 0; i < TM; ++i) a[g][i] = *reinterpret_cast<const bf16x8*>(abase + buf * STAGE + (i * 3 + g) * 1024);
   };
-  auto ldB = [&](pbf16x8 (&b)[3], int buf, int j) {
+  auto ldB = [&](bf16x8 (&b)[3], int buf, int j) {
 #pragma unroll
-    for (int g = 0; g < 3; ++g) b[g] = *reinterpret_cast<const pbf16x8*>(bbase + buf * STAGE + (j * 3 + g) * 1024);
+    for (int g = 0; g < 3; ++g) b[g] = *reinterpret_cast<const bf16x8*>(bbase + buf * STAGE + (j * 3 + g) * 1024);
   };
   unsigned long long t_acc[3] = {0, 0, 0}, t_last = __builtin_amdgcn_s_memtime();
   const unsigned long long t_begin = t_last;
@@ -947,22 +729,22 @@ __global__ __launch_bounds__(256) void pack_ps_kernel(const float* __restrict__ 
   if constexpr (PL == 2) {          // F16X2: the two fp16 images of scale x (activations: 2^6, range-checked; weights: 2^w_scale_exp)
     float4 v0 = make_float4(v[0], v[1], v[2], v[3]), v1 = make_float4(v[4], v[5], v[6], v[7]);
     if (range_flag) {               // activations (scale 2^6): range-checked and saturated; weights carry their own exponent
-      if (ps_h2_out_of_range(v0) || ps_h2_out_of_range(v1)) *range_flag = 1;
+      if (h2_out_of_range(v0) || h2_out_of_range(v1)) *range_flag = 1;
       v0 = h2_clamp4(v0);
       v1 = h2_clamp4(v1);
     }
-    pf16x4 h0, l0, h1, l1;
-    ps_split2h(ps_scaled(v0, scale), h0, l0);
-    ps_split2h(ps_scaled(v1, scale), h1, l1);
-    *reinterpret_cast<pf16x8*>(d) = pf16x8{h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
-    *reinterpret_cast<pf16x8*>(d + 1024) = pf16x8{l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
+    f16x4 h0, l0, h1, l1;
+    split2h(scaled(v0, scale), h0, l0);
+    split2h(scaled(v1, scale), h1, l1);
+    *reinterpret_cast<f16x8*>(d) = f16x8{h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
+    *reinterpret_cast<f16x8*>(d + 1024) = f16x8{l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
   } else {
-    pbf16x4 h0, m0, l0, h1, m1, l1;
-    ps_split3(make_float4(v[0], v[1], v[2], v[3]), h0, m0, l0);
-    ps_split3(make_float4(v[4], v[5], v[6], v[7]), h1, m1, l1);
-    *reinterpret_cast<pbf16x8*>(d) = pbf16x8{h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
-    *reinterpret_cast<pbf16x8*>(d + 1024) = pbf16x8{m0[0], m0[1], m0[2], m0[3], m1[0], m1[1], m1[2], m1[3]};
-    *reinterpret_cast<pbf16x8*>(d + 2048) = pbf16x8{l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
+    bf16x4 h0, m0, l0, h1, m1, l1;
+    split3(make_float4(v[0], v[1], v[2], v[3]), h0, m0, l0);
+    split3(make_float4(v[4], v[5], v[6], v[7]), h1, m1, l1);
+    *reinterpret_cast<bf16x8*>(d) = bf16x8{h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
+    *reinterpret_cast<bf16x8*>(d + 1024) = bf16x8{m0[0], m0[1], m0[2], m0[3], m1[0], m1[1], m1[2], m1[3]};
+    *reinterpret_cast<bf16x8*>(d + 2048) = bf16x8{l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
   }
 }
 
@@ -1019,19 +801,19 @@ __global__ __launch_bounds__(256) void ln_stats_ps_kernel(const float* __restric
     if (k0 < K) {
       unsigned char* d = dst + ((long long)rb * (K / 16) + (k0 >> 4)) * (PL * 1024) + ((o & 1) * 32 + r) * 16;
       if constexpr (PL == 2) {
-        if (ps_h2_out_of_range(v[c][0]) || ps_h2_out_of_range(v[c][1])) *range_flag = 1;
-        pf16x4 h0, l0, h1, l1;
-        ps_split2h(ps_scaled_sat(v[c][0]), h0, l0);
-        ps_split2h(ps_scaled_sat(v[c][1]), h1, l1);
-        *reinterpret_cast<pf16x8*>(d) = pf16x8{h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
-        *reinterpret_cast<pf16x8*>(d + 1024) = pf16x8{l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
+        if (h2_out_of_range(v[c][0]) || h2_out_of_range(v[c][1])) *range_flag = 1;
+        f16x4 h0, l0, h1, l1;
+        split2h(scaled_sat(v[c][0]), h0, l0);
+        split2h(scaled_sat(v[c][1]), h1, l1);
+        *reinterpret_cast<f16x8*>(d) = f16x8{h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
+        *reinterpret_cast<f16x8*>(d + 1024) = f16x8{l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
       } else {
-        pbf16x4 h0, m0, l0, h1, m1, l1;
-        ps_split3(v[c][0], h0, m0, l0);
-        ps_split3(v[c][1], h1, m1, l1);
-        *reinterpret_cast<pbf16x8*>(d) = pbf16x8{h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
-        *reinterpret_cast<pbf16x8*>(d + 1024) = pbf16x8{m0[0], m0[1], m0[2], m0[3], m1[0], m1[1], m1[2], m1[3]};
-        *reinterpret_cast<pbf16x8*>(d + 2048) = pbf16x8{l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
+        bf16x4 h0, m0, l0, h1, m1, l1;
+        split3(v[c][0], h0, m0, l0);
+        split3(v[c][1], h1, m1, l1);
+        *reinterpret_cast<bf16x8*>(d) = bf16x8{h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
+        *reinterpret_cast<bf16x8*>(d + 1024) = bf16x8{m0[0], m0[1], m0[2], m0[3], m1[0], m1[1], m1[2], m1[3]};
+        *reinterpret_cast<bf16x8*>(d + 2048) = bf16x8{l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
       }
     }
   }
@@ -1135,8 +917,8 @@ __global__ __launch_bounds__(64 * NWM * NWN, 2) void igemm_psc_kernel(const ldmk
   const int Nb = p.N / 32;
   const long long samples = ((long long)p.M + p.rows_per_sample - 1) / p.rows_per_sample;
   const unsigned Mb_in = (unsigned)((samples * p.in_h * p.in_w + 31) / 32);
-  const pu32x4 rs_a = ps_rsrc(p.a_ps, Mb_in * (unsigned)Kb_in * (unsigned)UB);
-  const pu32x4 rs_b = ps_rsrc(p.w_ps, (unsigned)Nb * (unsigned)Kb_w * (unsigned)UB);
+  const u32x4 rs_a = buffer_rsrc(p.a_ps, Mb_in * (unsigned)Kb_in * (unsigned)UB);
+  const u32x4 rs_b = buffer_rsrc(p.w_ps, (unsigned)Nb * (unsigned)Kb_w * (unsigned)UB);
 
   // A units: per tap the byte offset of this lane's input pixel (k-slab 0, plane 0), or PS_OOB in the halo / past the last row
   unsigned toff[AI][9];
@@ -1201,21 +983,21 @@ __global__ __launch_bounds__(64 * NWM * NWN, 2) void igemm_psc_kernel(const ldmk
   for (int c = c_begin; c < c_end; ++c) {
 #pragma unroll
     for (int j = 0; j < 18; ++j) {
-      if (hi_wave) ps_wait_vm<PL * UHI * (NS - 2)>(); else ps_wait_vm<PL * ULO * (NS - 2)>();
+      if (hi_wave) wait_vm<PL * UHI * (NS - 2)>(); else wait_vm<PL * ULO * (NS - 2)>();
       asm volatile("s_barrier" ::: "memory");
       issue(j + 2 < 18 ? c : c + 1, (j + 2) % 18, (j + 2) % NS, sB + 2);
       ++sB;
       const unsigned char* sb = smem_ps + (j % NS) * STAGE + lane16;
-      pf16x8 a8[PL][TM];
+      f16x8 a8[PL][TM];
 #pragma unroll
       for (int g = 0; g < PL; ++g)
 #pragma unroll
-        for (int i = 0; i < TM; ++i) a8[g][i] = *reinterpret_cast<const pf16x8*>(sb + ((wm * TM + i) * PL + g) * 1024);
+        for (int i = 0; i < TM; ++i) a8[g][i] = *reinterpret_cast<const f16x8*>(sb + ((wm * TM + i) * PL + g) * 1024);
 #pragma unroll
       for (int jn = 0; jn < TN; ++jn) {
-        pf16x8 b8[PL];
+        f16x8 b8[PL];
 #pragma unroll
-        for (int g = 0; g < PL; ++g) b8[g] = *reinterpret_cast<const pf16x8*>(sb + ((FA + wn * TN + jn) * PL + g) * 1024);
+        for (int g = 0; g < PL; ++g) b8[g] = *reinterpret_cast<const f16x8*>(sb + ((FA + wn * TN + jn) * PL + g) * 1024);
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
           // F16X2: lo hi, hi lo, hi hi (planes: 0 = hi, 1 = lo) -- the order of igemm_kernel<BF = 4>
@@ -1232,7 +1014,7 @@ __global__ __launch_bounds__(64 * NWM * NWN, 2) void igemm_psc_kernel(const ldmk
       }
     }
   }
-  ps_wait_vm<0>();
+  wait_vm<0>();
   const int lean = ps_lean_form<TR>(p, splitk, (nfast & 2) != 0, m0 + (wm + 1) * 32 * TM, n0 + (wn + 1) * 32 * TN);
   if (lean == 1) ps_epilogue<TM, TN, TR, PL, false, 1>(p, acc, m0 + wm * 32 * TM, n0 + wn * 32 * TN, splitk, ks, 0, ws, lane);
   else if (lean == 2) ps_epilogue<TM, TN, TR, PL, false, 2>(p, acc, m0 + wm * 32 * TM, n0 + wn * 32 * TN, splitk, ks, 0, ws, lane);
@@ -1266,14 +1048,14 @@ __global__ __launch_bounds__(256) void gn_apply_ps_h2_kernel(const float* __rest
       v0 = make_float4(silu_f(v0.x), silu_f(v0.y), silu_f(v0.z), silu_f(v0.w));
       v1 = make_float4(silu_f(v1.x), silu_f(v1.y), silu_f(v1.z), silu_f(v1.w));
     }
-    if (ps_h2_out_of_range(v0) || ps_h2_out_of_range(v1)) *range_flag = 1;
+    if (h2_out_of_range(v0) || h2_out_of_range(v1)) *range_flag = 1;
   }
   unsigned char* d = dst + ((long long)rb * (C / 16) + (k0 >> 4)) * 2048 + ((o & 1) * 32 + r) * 16;
-  pf16x4 a0, l0, a1, l1;
-  ps_split2h(ps_scaled_sat(v0), a0, l0);
-  ps_split2h(ps_scaled_sat(v1), a1, l1);
-  *reinterpret_cast<pf16x8*>(d) = pf16x8{a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};
-  *reinterpret_cast<pf16x8*>(d + 1024) = pf16x8{l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
+  f16x4 a0, l0, a1, l1;
+  split2h(scaled_sat(v0), a0, l0);
+  split2h(scaled_sat(v1), a1, l1);
+  *reinterpret_cast<f16x8*>(d) = f16x8{a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};
+  *reinterpret_cast<f16x8*>(d + 1024) = f16x8{l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
 }
 
 template <int NWM, int NWN, int TM, int TN, bool TR>

@@ -15,6 +15,8 @@
 // vector, residual, folded LayerNorm, GEGLU, GroupNorm records) as igemm_kernel<BF = 3>, and every accumulator sees the same
 // sequence of matrix instructions as in its 32-deep-slice tiles (tile_cfg 1 / 5): bitwise equal results at equal split-K.
 #include "ldmk_common.h"
+#include "ldmk_split.h"
+#include "ldmk_epilogue.h"
 
 // Diagnostic build only (tools/ws_probe.hip defines LDMK_WS_STAMPS): per-wave cycle totals of the pipeline's phases go to
 // args.splitk_counters as [workgroup][wave][4] 64-bit ticks (producers: store, load issue, barrier wait; consumers: products,
@@ -26,28 +28,6 @@
 #endif
 
 namespace ldmk {
-
-typedef __bf16 wbf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 wbf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int wu32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ wbf16x4 ws_bf4(const float4& v) { return wbf16x4{(__bf16)v.x, (__bf16)v.y, (__bf16)v.z, (__bf16)v.w}; }
-__device__ __forceinline__ void ws_split3(const float4& v, wbf16x4& h, wbf16x4& m, wbf16x4& l) {
-  h = ws_bf4(v);
-  const float4 r = make_float4(v.x - (float)h[0], v.y - (float)h[1], v.z - (float)h[2], v.w - (float)h[3]);
-  m = ws_bf4(r);
-  l = ws_bf4(make_float4(r.x - (float)m[0], r.y - (float)m[1], r.z - (float)m[2], r.w - (float)m[3]));
-}
-
-__device__ __forceinline__ wu32x4 ws_rsrc(const void* ptr, unsigned bytes) {      // raw buffer descriptor, uniform -> SGPRs
-  const unsigned long long a = (unsigned long long)ptr;
-  wu32x4 r;
-  r.x = __builtin_amdgcn_readfirstlane((unsigned)a);
-  r.y = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32) & 0xFFFFu);
-  r.z = __builtin_amdgcn_readfirstlane(bytes);
-  r.w = 0x00020000u;
-  return r;
-}
 
 constexpr int WS_BM = 256;
 constexpr int WS_RS = 24;            // bf16 per LDS row: 16 k + 8 pad (48 B: 16 consecutive rows cover the 64 banks exactly once)
@@ -94,16 +74,16 @@ __global__ __launch_bounds__(512) void igemm_ws_kernel(const ldmk_igemm_args p, 
   auto ws_compute = [&](int st) {             // consumers: one 16-deep step, 6 TM TN matrix instructions
     const __bf16* Aw = smem_ws + st * STAGE + (wm * 64 + l31) * WS_RS + 8 * half;
     const __bf16* Bw = smem_ws + st * STAGE + 3 * AIMG + l31 * WS_RS + 8 * half;
-    wbf16x8 a8[3][TM];
+    bf16x8 a8[3][TM];
 #pragma unroll
     for (int g = 0; g < 3; ++g)
 #pragma unroll
-      for (int i = 0; i < TM; ++i) a8[g][i] = *reinterpret_cast<const wbf16x8*>(Aw + g * AIMG + i * 32 * WS_RS);
+      for (int i = 0; i < TM; ++i) a8[g][i] = *reinterpret_cast<const bf16x8*>(Aw + g * AIMG + i * 32 * WS_RS);
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
-      wbf16x8 b8[3];
+      bf16x8 b8[3];
 #pragma unroll
-      for (int g = 0; g < 3; ++g) b8[g] = *reinterpret_cast<const wbf16x8*>(Bw + g * BIMG + j * 32 * WS_RS);
+      for (int g = 0; g < 3; ++g) b8[g] = *reinterpret_cast<const bf16x8*>(Bw + g * BIMG + j * 32 * WS_RS);
 #pragma unroll
       for (int i = 0; i < TM; ++i) {
         // smallest partial products first (images: 0 = hi, 1 = mid, 2 = lo) -- the order of igemm_kernel<BF = 3>
@@ -163,10 +143,10 @@ __global__ __launch_bounds__(512) void igemm_ws_kernel(const ldmk_igemm_args p, 
     const long long a_rows_ = conv ? samples_ * p.in_h * p.in_w : (long long)p.M;
     // buffer descriptors as four SGPRs each (the loads below are inline asm: the compiler does not count them, the waits are
     // placed by hand -- see the pipeline)
-    const wu32x4 rs_a0 = ws_rsrc(a0, (unsigned)(a_rows_ * p.c0 * 4));
-    const wu32x4 rs_a1 = ws_rsrc(a1 ? a1 : a0, (unsigned)(a_rows_ * p.c1 * 4));
+    const u32x4 rs_a0 = buffer_rsrc(a0, (unsigned)(a_rows_ * p.c0 * 4));
+    const u32x4 rs_a1 = buffer_rsrc(a1 ? a1 : a0, (unsigned)(a_rows_ * p.c1 * 4));
     const __bf16* wx = reinterpret_cast<const __bf16*>(p.w_split) + (long long)bz * p.w_split_bstride;
-    const wu32x4 rs_wx = ws_rsrc(wx, (unsigned)(3LL * p.N * p.w_split_ld * 2));
+    const u32x4 rs_wx = buffer_rsrc(wx, (unsigned)(3LL * p.N * p.w_split_ld * 2));
     unsigned bxoff[BSI], bxlds[BSI];
   #pragma unroll
     for (int i = 0; i < BSI; ++i) {
@@ -185,8 +165,8 @@ __global__ __launch_bounds__(512) void igemm_ws_kernel(const ldmk_igemm_args p, 
     // it placed was vmcnt(0), which also waited for the younger set: 2650 cycles per stage in split+store, consumers idle
     // 1320 of 3500 -- s_memtime stamps, tools/ws_probe.hip.)  Every stage issues exactly NL loads (stages past the end read
     // out of range: zeros, no memory traffic), so the count is a constant.
-    wu32x4 areg0[WS_AR], areg1[WS_AR], breg0[BSI], breg1[BSI];
-    auto ws_load = [&](int s, wu32x4 (&areg)[WS_AR], wu32x4 (&breg)[BSI]) {     // issue the NL loads of local stage s
+    u32x4 areg0[WS_AR], areg1[WS_AR], breg0[BSI], breg1[BSI];
+    auto ws_load = [&](int s, u32x4 (&areg)[WS_AR], u32x4 (&breg)[BSI]) {     // issue the NL loads of local stage s
       const bool live = s < n16;
       const int kc = it_begin + (s >> 1), h16 = s & 1;
       int tap = 0, cc = kc;
@@ -202,13 +182,13 @@ __global__ __launch_bounds__(512) void igemm_ws_kernel(const ldmk_igemm_args p, 
       for (int i = 0; i < WS_AR; ++i) oa[i] = (live && (r_mask[i] & tbit)) ? (second ? aoff1[i] : aoff0[i]) + sa : 0xFFFFFFFFu;
   #pragma unroll
       for (int i = 0; i < BSI; ++i) ob[i] = (live && bxoff[i] != 0xFFFFFFFFu) ? bxoff[i] + sb : 0xFFFFFFFFu;
-      const wu32x4 rs_a = second ? rs_a1 : rs_a0;
+      const u32x4 rs_a = second ? rs_a1 : rs_a0;
   #pragma unroll
       for (int i = 0; i < WS_AR; ++i) asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen" : "=v"(areg[i]) : "v"(oa[i]), "s"(rs_a) : "memory");
   #pragma unroll
       for (int i = 0; i < BSI; ++i) asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen" : "=v"(breg[i]) : "v"(ob[i]), "s"(rs_wx) : "memory");
     };
-    auto ws_wait = [&](wu32x4 (&areg)[WS_AR], wu32x4 (&breg)[BSI]) {            // the older set has landed (names its registers)
+    auto ws_wait = [&](u32x4 (&areg)[WS_AR], u32x4 (&breg)[BSI]) {            // the older set has landed (names its registers)
       static_assert(NL == 7 || NL == 8, "the wait below is written for 7 or 8 loads per stage");
       if constexpr (NL == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
       else asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
@@ -217,7 +197,7 @@ __global__ __launch_bounds__(512) void igemm_ws_kernel(const ldmk_igemm_args p, 
   #pragma unroll
       for (int i = 0; i < BSI; ++i) asm volatile("" : "+v"(breg[i]));
     };
-    auto ws_store = [&](int s, int st, wu32x4 (&araw)[WS_AR], wu32x4 (&breg)[BSI]) {   // prologue + split + LDS stores of stage s into buffer st
+    auto ws_store = [&](int s, int st, u32x4 (&araw)[WS_AR], u32x4 (&breg)[BSI]) {   // prologue + split + LDS stores of stage s into buffer st
       __bf16* base = smem_ws + st * STAGE;
       float4 areg[WS_AR];
   #pragma unroll
@@ -257,16 +237,16 @@ __global__ __launch_bounds__(512) void igemm_ws_kernel(const ldmk_igemm_args p, 
       }
   #pragma unroll
       for (int i = 0; i < WS_AR; ++i) {
-        wbf16x4 h, m, l;
-        ws_split3(areg[i], h, m, l);
+        bf16x4 h, m, l;
+        split3(areg[i], h, m, l);
         __bf16* d = base + (arow + 64 * i) * WS_RS + acol;
-        *reinterpret_cast<wbf16x4*>(d) = h;
-        *reinterpret_cast<wbf16x4*>(d + AIMG) = m;
-        *reinterpret_cast<wbf16x4*>(d + 2 * AIMG) = l;
+        *reinterpret_cast<bf16x4*>(d) = h;
+        *reinterpret_cast<bf16x4*>(d + AIMG) = m;
+        *reinterpret_cast<bf16x4*>(d + 2 * AIMG) = l;
       }
   #pragma unroll
       for (int i = 0; i < BSI; ++i) {
-        if (ptid + 256 * i < BITEMS) *reinterpret_cast<wu32x4*>(reinterpret_cast<char*>(base) + bxlds[i]) = breg[i];
+        if (ptid + 256 * i < BITEMS) *reinterpret_cast<u32x4*>(reinterpret_cast<char*>(base) + bxlds[i]) = breg[i];
       }
     };
 
@@ -330,121 +310,16 @@ __global__ __launch_bounds__(512) void igemm_ws_kernel(const ldmk_igemm_args p, 
   if (lane == 0) { ws_dbg[0] = ws_acc[0]; ws_dbg[1] = ws_acc[1]; ws_dbg[2] = ws_acc[2]; ws_dbg[3] = __builtin_amdgcn_s_memtime() - ws_t0; }
 #endif
 
-  // ---- epilogue (consumers).  C/D map: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
+  // ---- epilogue (consumers): the lane = column forms of csrc/ldmk_epilogue.h, general form only
   const int rowbase = m0 + wm * 64;
   const int colbase = n0;
-  if (splitk > 1) {   // raw partial slab [ks][M][N]; igemm_reduce_kernel (or the consumer, raw_slabs) sums them
-    float* slab = ws + ((long long)bz * splitk + ks) * p.M * p.N;
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      const int col = colbase + j * 32 + l31;
-      if (col >= p.N) continue;
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int row = rowbase + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-          if (row < p.M) slab[(long long)row * p.N + col] = acc[i][j][r];
-        }
-    }
+  if (splitk > 1) {   // igemm_reduce_kernel (or the consumer, raw_slabs) sums the slabs
+    col_slab_store<TM, TN>(p, acc, rowbase, colbase, bz, l31, half, splitk, ks, ws);
     return;
   }
-  float* __restrict__ outp = p.out + (long long)bz * p.out_bstride;
-  const float* resp = p.residual ? p.residual + (long long)bz * p.out_bstride : nullptr;
-  const float alpha = p.alpha;
   const bool lnf = p.a_tf == LDMK_TF_LAYERNORM_FOLDED;
-  const float2* __restrict__ stats2 = reinterpret_cast<const float2*>(p.row_stats);
-  if (p.epi == LDMK_EPI_GEGLU) {
-    if constexpr (TN % 2 == 0) {
-#pragma unroll
-      for (int j = 0; j < TN; j += 2) {
-        const int cv = colbase + j * 32 + l31;        // packed value column
-        const int cg = cv + 32;                       // packed gate column
-        if (cv >= p.N) continue;
-        const int oc = ((colbase + j * 32) >> 1) + l31;
-        const float bv = p.bias ? p.bias[cv] : 0.f, bg = p.bias ? p.bias[cg] : 0.f;
-        const float csv = lnf ? p.ln_colsum[cv] : 0.f, csg = lnf ? p.ln_colsum[cg] : 0.f;
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-          float2 st[16];
-          if (lnf) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) st[r] = stats2[min(rowbase + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half, p.M - 1)];
-          }
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int row = rowbase + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-            if (row < p.M) {
-              float v = acc[i][j][r] * alpha, g = acc[i][j + 1][r] * alpha;
-              if (lnf) {      // same arithmetic as igemm.hip / rgemm.hip / igemm_reduce_kernel
-                v = fmaf(-st[r].x, csv, v) * st[r].y;
-                g = fmaf(-st[r].x, csg, g) * st[r].y;
-              }
-              v += bv;
-              g += bg;
-              outp[(long long)row * p.ldc + oc] = v * gelu_erf_f(g);
-            }
-          }
-        }
-      }
-    }
-    return;
-  }
-  const bool tile_in_sample = p.rows_per_sample % 32 == 0;
-  int smp[TM];
-#pragma unroll
-  for (int i = 0; i < TM; ++i) smp[i] = p.batch_vec ? min(rowbase + i * 32, p.M - 1) / p.rows_per_sample : 0;
-#pragma unroll
-  for (int j = 0; j < TN; ++j) {
-    const int col = colbase + j * 32 + l31;
-    if (col >= p.N) continue;
-    const float bv = p.bias ? p.bias[col] : 0.f;
-    const float cs = lnf ? p.ln_colsum[col] : 0.f;
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-      float vals[16];
-      const int r0 = rowbase + i * 32 + 4 * half;
-      if (lnf) {
-        float2 st[16];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) st[r] = stats2[min(r0 + (r & 3) + 8 * (r >> 2), p.M - 1)];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][j][r] = fmaf(-st[r].x, cs, acc[i][j][r] * alpha) * st[r].y;
-      }
-      const unsigned obase = (unsigned)r0 * (unsigned)p.ldc + (unsigned)col;
-      const float vec = (p.batch_vec && tile_in_sample) ? p.batch_vec[(long long)smp[i] * p.batch_vec_ld + col] : 0.f;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int dr = (r & 3) + 8 * (r >> 2);
-        float v = 0.f;
-        if (r0 + dr < p.M) {
-          v = (lnf ? acc[i][j][r] : acc[i][j][r] * alpha) + bv;
-          if (p.batch_vec) v += tile_in_sample ? vec : p.batch_vec[(long long)((r0 + dr) / p.rows_per_sample) * p.batch_vec_ld + col];
-          const unsigned o = obase + (unsigned)(dr * p.ldc);
-          if (resp) v += resp[o];
-          outp[o] = v;
-        }
-        vals[r] = v;
-      }
-      if (p.stats_out && rowbase + i * 32 < p.M) {
-        // GroupNorm partial record of this 32-row tile x column (the record of gn_partial_kernel / igemm_kernel)
-        const float shift = __shfl(vals[0], l31, 64);      // row 0 of the tile
-        float sm = 0.f, sq = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const float d = vals[r] - shift;
-          sm += d;
-          sq = fmaf(d, d, sq);
-        }
-        sm += __shfl_xor(sm, 32, 64);
-        sq += __shfl_xor(sq, 32, 64);
-        if (half == 0) {
-          float* d = p.stats_out + ((long long)((rowbase + i * 32) >> 5) * p.N + col) * 3;
-          d[0] = shift; d[1] = sm; d[2] = sq;
-        }
-      }
-    }
-  }
+  if (p.epi == LDMK_EPI_GEGLU) col_geglu<TM, TN>(p, acc, rowbase, colbase, bz, l31, half, lnf);
+  else col_general<TM, TN>(p, acc, rowbase, colbase, bz, l31, half, lnf);
 }
 
 int launch_splitk_reduce(const ldmk_igemm_args& a, int splitk, float* ws, hipStream_t st);

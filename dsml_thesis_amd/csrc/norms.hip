@@ -1,6 +1,7 @@
 // GroupNorm / LayerNorm statistics (HBM-bound; the normalisation itself is applied by the
 // consumer while it stages its A operand, see igemm.hip).
 #include "ldmk_common.h"
+#include "ldmk_split.h"
 
 namespace ldmk {
 
@@ -85,7 +86,6 @@ __global__ __launch_bounds__(256) void gn_finalize_kernel(const float* __restric
 
 // LayerNorm statistics: one half-wave (32 lanes x float4 = 512 B per load instruction) per row, exact
 // two-pass in registers (C <= 1024, C % 4 == 0); the generic scalar form handles other widths.
-typedef __bf16 nbf16x4 __attribute__((ext_vector_type(4)));
 // SPLIT: also write the row as the three bf16 images of its exact split x = hi + mid + lo (round to nearest even, the split
 // igemm_kernel<BF = 3> makes while staging): split[img][row][ld], the a_split operand of LDMK_COMPUTE_BF16X3
 // GUARD (flag != nullptr): rows whose |mean| exceeds `guard` standard deviations set *flag -- the consumer that folds the
@@ -135,14 +135,12 @@ __global__ __launch_bounds__(256) void ln_stats_kernel(const float* __restrict__
       for (int i = 0; i < 8; ++i) {
         const int c4 = l31 + 32 * i;
         if (c4 < c4n) {
-          const nbf16x4 h = {(__bf16)v[i].x, (__bf16)v[i].y, (__bf16)v[i].z, (__bf16)v[i].w};
-          const float r0 = v[i].x - (float)h[0], r1 = v[i].y - (float)h[1], r2 = v[i].z - (float)h[2], r3 = v[i].w - (float)h[3];
-          const nbf16x4 m = {(__bf16)r0, (__bf16)r1, (__bf16)r2, (__bf16)r3};
-          const nbf16x4 l = {(__bf16)(r0 - (float)m[0]), (__bf16)(r1 - (float)m[1]), (__bf16)(r2 - (float)m[2]), (__bf16)(r3 - (float)m[3])};
+          bf16x4 h, m, l;
+          split3(v[i], h, m, l);
           __bf16* d = split + row * ld_split + 4 * c4;
-          *reinterpret_cast<nbf16x4*>(d) = h;
-          *reinterpret_cast<nbf16x4*>(d + img) = m;
-          *reinterpret_cast<nbf16x4*>(d + 2 * img) = l;
+          *reinterpret_cast<bf16x4*>(d) = h;
+          *reinterpret_cast<bf16x4*>(d + img) = m;
+          *reinterpret_cast<bf16x4*>(d + 2 * img) = l;
         }
       }
     }

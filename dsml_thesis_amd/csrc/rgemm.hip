@@ -25,7 +25,8 @@
 // Results are deterministic (fixed k order per tile shape); the K-summation order differs from the LDS-tiled
 // kernel's only in the order of the 8 addends inside each 8-deep block.
 #include "ldmk_common.h"
-#include <type_traits>
+#include "ldmk_split.h"
+#include "ldmk_epilogue.h"
 
 // Diagnostic build only (tools/rgemm_probe.hip defines LDMK_RG_STAMPS): per-wave s_memtime stamps around the
 // prologue / main loop / epilogue go to args.splitk_ws (unused by this kernel), [wave][4] 64-bit ticks.
@@ -36,14 +37,6 @@
 #endif
 
 namespace ldmk {
-
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    static_for<I + 1, N>(f);
-  }
-}
 
 // global_load_dwordx4 with an immediate byte offset (13-bit signed).  hipcc does not count this load: every use of `d`
 // sits behind wait_all() below.
@@ -280,7 +273,7 @@ __global__ __launch_bounds__(256) void rgemm_kernel(const ldmk_igemm_args p, con
   float rv[RSETS][16];                                          // residual of the tile in work / of the next one
   // FULL (wave-uniform: the wave's 32 TM rows lie inside M) and HASR / HASV (a residual / a per-sample vector is present) are
   // compile-time in the body below: no row predicate around every store, no operand branches between them (round 5, as in the
-  // lean epilogues of igemm.hip / igemm_ps.hip; same arithmetic, same order)
+  // lean epilogues of csrc/ldmk_epilogue.h / igemm_ps.hip; same arithmetic, same order)
   auto finish = [&](auto FULL_, auto HASR_, auto HASV_) {
     constexpr bool FULL = decltype(FULL_)::value, HASR = decltype(HASR_)::value, HASV = decltype(HASV_)::value;
     auto load_residual = [&](auto T) {
@@ -308,28 +301,13 @@ __global__ __launch_bounds__(256) void rgemm_kernel(const ldmk_igemm_args p, con
         const int dr = i * 32 + (r & 3) + 8 * (r >> 2);
         float v = acc[i][j][r] * alpha;
         if constexpr (lnf) v = fmaf(-st[i][r].x, cs[j], v) * st[i][r].y;
-        v += bias[j];                                             // same association as igemm.hip
+        v += bias[j];                                             // same association as col_general (ldmk_epilogue.h)
         if constexpr (HASV) v += vec[j];
         if constexpr (HASR) v += rv[t % RSETS][r];
         vals[r] = v;
         if (FULL || rlane + dr < p.M) outp[obase + (unsigned)(dr * p.ldc)] = v;
       }
-      if (p.stats_out && (FULL || row0 + i * 32 < p.M)) {
-        const float shift = __shfl(vals[0], l31, 64);           // row 0 of the 32-row tile
-        float sm = 0.f, sq = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const float d = vals[r] - shift;
-          sm += d;
-          sq = fmaf(d, d, sq);
-        }
-        sm += __shfl_xor(sm, 32, 64);
-        sq += __shfl_xor(sq, 32, 64);
-        if (half == 0) {
-          float* d = p.stats_out + ((long long)((row0 + i * 32) >> 5) * p.N + col) * 3;
-          d[0] = shift; d[1] = sm; d[2] = sq;
-        }
-      }
+      if (p.stats_out && (FULL || row0 + i * 32 < p.M)) gn_tile_record(vals, p.stats_out, (row0 + i * 32) >> 5, p.N, col, l31, half);
     });
   };
   using T_ = std::true_type;

@@ -23,6 +23,7 @@
 // the chip streams its own 1/1280 of the 14.7 MB weight matrix, once.
 // Deterministic: the k order inside a wave, the tree and the slab order are all fixed.
 #include "ldmk_common.h"
+#include "ldmk_epilogue.h"
 #include <type_traits>
 
 // Diagnostic build only (tools/sgemm_probe.py builds a second library with -DLDMK_SG_STAMPS): per-wave s_memrealtime stamps
@@ -313,7 +314,7 @@ __global__ __launch_bounds__(64 * NW) void sgemm_kernel(const ldmk_igemm_args p,
           const float2 st = stats2[row];
           v = fmaf(-st.x, cs, v) * st.y;
         }
-        v += bias;                                                // same association as igemm.hip / rgemm.hip
+        v += bias;                                                // same association as col_general (ldmk_epilogue.h) / rgemm.hip
         if (bvec) v += vec;
         if (p.residual) v += p.residual[(long long)row * p.ldc + col];
         vals[r] = v;
@@ -323,22 +324,8 @@ __global__ __launch_bounds__(64 * NW) void sgemm_kernel(const ldmk_igemm_args p,
         const int row = rlane + i * 32 + (r & 3) + 8 * (r >> 2);
         if (row < p.M) p.out[(long long)row * p.ldc + col] = vals[r];
       }
-      if (p.stats_out && row0 + i * 32 < p.M) {                   // GroupNorm partial record of this 32-row tile and column
-        const float shift = __shfl(vals[0], l31, 64);
-        float sm = 0.f, sq = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const float d = vals[r] - shift;
-          sm += d;
-          sq = fmaf(d, d, sq);
-        }
-        sm += __shfl_xor(sm, 32, 64);
-        sq += __shfl_xor(sq, 32, 64);
-        if (half == 0) {
-          float* d = p.stats_out + ((long long)((row0 + i * 32) >> 5) * p.N + col) * 3;
-          d[0] = shift; d[1] = sm; d[2] = sq;
-        }
-      }
+      // GroupNorm partial record of this 32-row tile and column (csrc/ldmk_epilogue.h)
+      if (p.stats_out && row0 + i * 32 < p.M) gn_tile_record(vals, p.stats_out, (row0 + i * 32) >> 5, p.N, col, l31, half);
     }
   }
 }

@@ -9,12 +9,10 @@
 // the optimizer updates packed weights in place.  The output is small and the reduction long: the rows are split
 // over blockIdx.y (`splitr`) into partial slabs that a second kernel sums in a fixed order (bitwise reproducible).
 #include "ldmk_common.h"
+#include "ldmk_split.h"
 #include <stdlib.h>
 
 namespace ldmk {
-
-typedef __bf16 wbf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 wbf16x8 __attribute__((ext_vector_type(8)));
 
 // BF = true: bf16 matrix-core compute (BASELINE configs[4]).  Staging is the fp32 kernel's, unchanged (float4 loads, one
 // index computation per 16 bytes, r-major fp32 LDS slices).  The MFMA's K dimension is the ROW index r here, so a bf16
@@ -144,7 +142,7 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const ldmk_wgrad_args p, con
       const float* Bg = Bs + (8 * half) * BSTR + wn * (32 * TN) + l31;
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
-        wbf16x8 a8[TM], b8[TN];
+        bf16x8 a8[TM], b8[TN];
 #pragma unroll
         for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -314,10 +312,10 @@ __global__ __launch_bounds__(256) void wgrad_tr_kernel(const ldmk_wgrad_args p, 
   auto store_slice = [&](int buf) {                 // rounded to bf16 (RNE) once, here
 #pragma unroll
     for (int i = 0; i < NA; ++i)
-      *reinterpret_cast<wbf16x4*>(&At[buf][a_rl[i] * AS + a_col[i]]) = wbf16x4{(__bf16)areg[i].x, (__bf16)areg[i].y, (__bf16)areg[i].z, (__bf16)areg[i].w};
+      *reinterpret_cast<bf16x4*>(&At[buf][a_rl[i] * AS + a_col[i]]) = bf16x4{(__bf16)areg[i].x, (__bf16)areg[i].y, (__bf16)areg[i].z, (__bf16)areg[i].w};
 #pragma unroll
     for (int i = 0; i < NB; ++i) {
-      *reinterpret_cast<wbf16x4*>(&Bt[buf][b_rl[i] * BS + b_col[i]]) = wbf16x4{(__bf16)breg[i].x, (__bf16)breg[i].y, (__bf16)breg[i].z, (__bf16)breg[i].w};
+      *reinterpret_cast<bf16x4*>(&Bt[buf][b_rl[i] * BS + b_col[i]]) = bf16x4{(__bf16)breg[i].x, (__bf16)breg[i].y, (__bf16)breg[i].z, (__bf16)breg[i].w};
       bsum[i].x += breg[i].x; bsum[i].y += breg[i].y; bsum[i].z += breg[i].z; bsum[i].w += breg[i].w;
     }
   };
@@ -336,10 +334,10 @@ __global__ __launch_bounds__(256) void wgrad_tr_kernel(const ldmk_wgrad_args p, 
   const int tr_row = 8 * (g16 >> 1) + (j16 >> 2), tr_col = 16 * (g16 & 1) + 4 * (j16 & 3);
   const int a_off = tr_row * AS + wm * (32 * TM) + tr_col;
   const int b_off = tr_row * BS + wn * (32 * TN) + tr_col;
-  auto tr8 = [](const __bf16* q, int stride4) -> wbf16x8 {       // rows +0..3 and +4..7 of this lane's column
+  auto tr8 = [](const __bf16* q, int stride4) -> bf16x8 {       // rows +0..3 and +4..7 of this lane's column
     const ws16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ws16x4 __attribute__((address_space(3)))*)(q));
     const ws16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ws16x4 __attribute__((address_space(3)))*)(q + stride4));
-    return __builtin_bit_cast(wbf16x8, ws16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]});
+    return __builtin_bit_cast(bf16x8, ws16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]});
   };
 
   if (it_begin < it_end) {
@@ -353,7 +351,7 @@ __global__ __launch_bounds__(256) void wgrad_tr_kernel(const ldmk_wgrad_args p, 
     if (more) load_slice(it + 1);
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
-      wbf16x8 a8[TM], b8[TN];
+      bf16x8 a8[TM], b8[TN];
 #pragma unroll
       for (int i = 0; i < TM; ++i) a8[i] = tr8(&At[buf][a_off + 16 * s * AS + 32 * i], 4 * AS);
 #pragma unroll

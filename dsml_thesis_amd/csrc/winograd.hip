@@ -14,6 +14,7 @@
 // tensors; the output transform takes over the convolution's epilogue: bias, per-sample (timestep-embedding) vector,
 // residual, and the GroupNorm partial records of the result for the next layer.
 #include "ldmk_common.h"
+#include "ldmk_split.h"
 
 namespace ldmk {
 
@@ -82,27 +83,25 @@ __global__ __launch_bounds__(256) void wino_input_kernel(const float* __restrict
 // instruction writes ONE whole fragment plane, 1 KiB contiguous; a workgroup = 32 tiles x 4 k-slabs.  Same arithmetic (and
 // order) as wino_input_kernel: V is bit for bit the same matrix, split exactly.
 // PL = 2: the F16X2 form of the layout (two fp16 planes of 2^6 x per 2-KiB unit; an element of 1000 or more raises *range_flag).
-typedef __bf16 wbf16x8_ __attribute__((ext_vector_type(8)));
-typedef _Float16 wf16x8_ __attribute__((ext_vector_type(8)));
 template <int PL = 3>
 __device__ __forceinline__ void wino_store_ps(unsigned char* d, const float4& a, const float4& b, int* range_flag = nullptr) {
   float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
   if constexpr (PL == 2) {
-    wf16x8_ h, l;
+    f16x8 h, l;
     bool bad = false;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      bad |= (__float_as_uint(v[e]) & 0x7fffffffu) >= 0x447a0000u;
-      const float s = h2_clamp(v[e]) * 64.f;      // (saturated: ldmk_common.h)
+      bad |= h2_out_of_range(v[e]);
+      const float s = h2_clamp(v[e]) * H2_SCALE;      // (saturated: ldmk_common.h)
       h[e] = (_Float16)s;
       l[e] = (_Float16)(s - (float)h[e]);
     }
     if (bad) *range_flag = 1;
-    *reinterpret_cast<wf16x8_*>(d) = h;
-    *reinterpret_cast<wf16x8_*>(d + 1024) = l;
+    *reinterpret_cast<f16x8*>(d) = h;
+    *reinterpret_cast<f16x8*>(d + 1024) = l;
     return;
   }
-  wbf16x8_ h, m, l;
+  bf16x8 h, m, l;
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
     h[e] = (__bf16)v[e];
@@ -110,9 +109,9 @@ __device__ __forceinline__ void wino_store_ps(unsigned char* d, const float4& a,
     m[e] = (__bf16)r;
     l[e] = (__bf16)(r - (float)m[e]);
   }
-  *reinterpret_cast<wbf16x8_*>(d) = h;
-  *reinterpret_cast<wbf16x8_*>(d + 1024) = m;
-  *reinterpret_cast<wbf16x8_*>(d + 2048) = l;
+  *reinterpret_cast<bf16x8*>(d) = h;
+  *reinterpret_cast<bf16x8*>(d + 1024) = m;
+  *reinterpret_cast<bf16x8*>(d + 2048) = l;
 }
 
 template <int PL>
