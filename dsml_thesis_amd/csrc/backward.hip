@@ -155,6 +155,194 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const float* __restri
   }
 }
 
+// ---- FiLM GroupNorm backward (use_scale_shift_norm, openaimodel.py:267-271) ------------------------------------------
+// h = SiLU(v), v = u (1 + s) + t, u = xhat gamma + beta, xhat = (x - mean) rstd, (s | t) = the block's emb_layers row of the sample.
+// With dv = dy SiLU'(v) every gradient follows from the SAME two per-(sample, channel) sums the plain backward needs,
+//   A = sum_p dv,  B = sum_p dv xhat :
+//   dt = A,  ds = gamma B + beta A,  dbeta = sum_n (1 + s) A,  dgamma = sum_n (1 + s) B,
+//   dx = sc' dv - rstd (m1 + xhat m2),  sc' = gamma rstd (1 + s) (the folded coefficient the forward applied),
+//   m1, m2 = group means of gamma (1 + s) A and gamma (1 + s) B.
+// So: one reduction pass over x and dy (16-byte loads, A and B only), a per-(sample, group) finalize that also writes d(s | t),
+// and the apply pass.  Single source (the block's h1), C % 4 == 0.  Every sum has a fixed order; no atomics.
+constexpr int GF_PIX = 64;   // pixels per partial record
+
+__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+
+// pass 1: 16 float4 columns (64 channels) x 16 pixel lanes per workgroup; a wave reads 4 pixel rows x 256 contiguous bytes.
+// The four pixel lanes of a wave fold through the wave (lanes l, l^16, l^32, l^48), the four waves through LDS.
+__global__ __launch_bounds__(256) void gn_film_bwd_partial_kernel(const float* __restrict__ x, const float* __restrict__ dy,
+                                                                  const float* __restrict__ coef, const float* __restrict__ mr,
+                                                                  int C, int hw, int groups, float* __restrict__ partial) {
+  __shared__ float4 red[4][16][2];
+  const int cpg = C / groups;
+  const int cl = threadIdx.x & 15, pl = threadIdx.x >> 4, wave = threadIdx.x >> 6;
+  const int c = blockIdx.x * 64 + cl * 4, chunk = blockIdx.y, n = blockIdx.z, chunks = gridDim.y;
+  float a[4] = {0.f, 0.f, 0.f, 0.f}, b[4] = {0.f, 0.f, 0.f, 0.f};
+  if (c < C) {
+    const float4 sc4 = ld4(coef + ((long long)n * 2) * C + c), sh4 = ld4(coef + ((long long)n * 2 + 1) * C + c);
+    const float sc[4] = {sc4.x, sc4.y, sc4.z, sc4.w}, sh[4] = {sh4.x, sh4.y, sh4.z, sh4.w};
+    float mean[4], rstd[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int g = (c + j) / cpg;
+      mean[j] = mr[((long long)n * groups + g) * 2];
+      rstd[j] = mr[((long long)n * groups + g) * 2 + 1];
+    }
+    const int p0 = chunk * GF_PIX, p1 = min(hw, p0 + GF_PIX);
+    for (int p = p0 + pl; p < p1; p += 16) {
+      const long long o = ((long long)n * hw + p) * C + c;
+      const float4 x4 = ld4(x + o), d4 = ld4(dy + o);
+      const float xv[4] = {x4.x, x4.y, x4.z, x4.w}, dv[4] = {d4.x, d4.y, d4.z, d4.w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float dz = dv[j] * dsilu_f(fmaf(xv[j], sc[j], sh[j]));
+        a[j] += dz;
+        b[j] = fmaf(dz, (xv[j] - mean[j]) * rstd[j], b[j]);
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    a[j] += __shfl_xor(a[j], 16, 64);
+    a[j] += __shfl_xor(a[j], 32, 64);
+    b[j] += __shfl_xor(b[j], 16, 64);
+    b[j] += __shfl_xor(b[j], 32, 64);
+  }
+  if ((threadIdx.x & 63) < 16) {
+    red[wave][cl][0] = make_float4(a[0], a[1], a[2], a[3]);
+    red[wave][cl][1] = make_float4(b[0], b[1], b[2], b[3]);
+  }
+  __syncthreads();
+  if (threadIdx.x < 16 && c < C) {
+    float* d = partial + (((long long)n * chunks + chunk) * 2) * C + c;        // [n][chunks][A | B][C]
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const float4 r0 = red[0][cl][k], r1 = red[1][cl][k], r2 = red[2][cl][k], r3 = red[3][cl][k];
+      *reinterpret_cast<float4*>(d + (long long)k * C) =
+          make_float4((r0.x + r1.x) + (r2.x + r3.x), (r0.y + r1.y) + (r2.y + r3.y), (r0.z + r1.z) + (r2.z + r3.z),
+                      (r0.w + r1.w) + (r2.w + r3.w));
+    }
+  }
+}
+
+// pass 2: one wave per (sample, group).  Totals over the chunks -> d(scale | shift) of the sample, the (1 + s)-weighted totals the
+// parameter sums read (gn_bwd_params_kernel), and the three per-channel planes (mean, rstd m1, rstd^2 m2) the apply pass reads.
+__global__ __launch_bounds__(256) void gn_film_bwd_finalize_kernel(const float* __restrict__ partial, int C, int hw, int chunks,
+                                                                   int groups, const float* __restrict__ gamma,
+                                                                   const float* __restrict__ beta, const float* __restrict__ mr,
+                                                                   const float* __restrict__ film, int film_ld,
+                                                                   float* __restrict__ tot, float* __restrict__ cf,
+                                                                   float* __restrict__ dfilm, int dfilm_ld) {
+  const int n = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6, cpg = C / groups;
+  for (int g = blockIdx.x * 4 + wave; g < groups; g += gridDim.x * 4) {
+    float s1 = 0.f, s2 = 0.f;
+    for (int cc = lane; cc < cpg; cc += 64) {
+      const int c = g * cpg + cc;
+      float a = 0.f, b = 0.f;
+      for (int ch = 0; ch < chunks; ++ch) {
+        const float* d = partial + (((long long)n * chunks + ch) * 2) * C + c;
+        a += d[0]; b += d[C];
+      }
+      const float f = 1.0f + film[(long long)n * film_ld + c];
+      dfilm[(long long)n * dfilm_ld + c] = fmaf(gamma[c], b, beta[c] * a);
+      dfilm[(long long)n * dfilm_ld + C + c] = a;
+      a *= f; b *= f;
+      tot[((long long)n * C + c) * 2] = a;
+      tot[((long long)n * C + c) * 2 + 1] = b;
+      s1 = fmaf(gamma[c], a, s1);
+      s2 = fmaf(gamma[c], b, s2);
+    }
+    s1 = wave_sum(s1);
+    s2 = wave_sum(s2);
+    const float inv = 1.0f / ((float)cpg * (float)hw);
+    const float mean = mr[((long long)n * groups + g) * 2], rstd = mr[((long long)n * groups + g) * 2 + 1];
+    const float k1 = rstd * (s1 * inv), k2 = rstd * rstd * (s2 * inv);
+    for (int cc = lane; cc < cpg; cc += 64) {
+      const int c = g * cpg + cc;
+      cf[((long long)n * 3) * C + c] = mean;
+      cf[((long long)n * 3 + 1) * C + c] = k1;
+      cf[((long long)n * 3 + 2) * C + c] = k2;
+    }
+  }
+}
+
+// pass 3: dx (+)= sc' dv - (k1 + (x - mean) k2), 16 bytes per lane
+__global__ __launch_bounds__(256) void gn_film_bwd_apply_kernel(const float* __restrict__ x, const float* __restrict__ dy,
+                                                                const float* __restrict__ coef, const float* __restrict__ cf,
+                                                                int C, int hw, float* __restrict__ dx, int acc, long long total4) {
+  const int c4n = C >> 2;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total4; i += (long long)gridDim.x * blockDim.x) {
+    const long long row = i / c4n;
+    const int c = (int)(i - row * c4n) * 4, n = (int)(row / hw);
+    const long long o = row * C + c;
+    const float4 x4 = ld4(x + o), d4 = ld4(dy + o);
+    const float4 sc = ld4(coef + ((long long)n * 2) * C + c), sh = ld4(coef + ((long long)n * 2 + 1) * C + c);
+    const float4 mean = ld4(cf + ((long long)n * 3) * C + c), k1 = ld4(cf + ((long long)n * 3 + 1) * C + c),
+                 k2 = ld4(cf + ((long long)n * 3 + 2) * C + c);
+    float4 v;
+    v.x = sc.x * (d4.x * dsilu_f(fmaf(x4.x, sc.x, sh.x))) - fmaf(x4.x - mean.x, k2.x, k1.x);
+    v.y = sc.y * (d4.y * dsilu_f(fmaf(x4.y, sc.y, sh.y))) - fmaf(x4.y - mean.y, k2.y, k1.y);
+    v.z = sc.z * (d4.z * dsilu_f(fmaf(x4.z, sc.z, sh.z))) - fmaf(x4.z - mean.z, k2.z, k1.z);
+    v.w = sc.w * (d4.w * dsilu_f(fmaf(x4.w, sc.w, sh.w))) - fmaf(x4.w - mean.w, k2.w, k1.w);
+    if (acc) {
+      const float4 old = ld4(dx + o);
+      v.x += old.x; v.y += old.y; v.z += old.z; v.w += old.w;
+    }
+    *reinterpret_cast<float4*>(dx + o) = v;
+  }
+}
+
+// ---- label embedding backward: dW[y[i]] (+)= d_emb[i] (openaimodel.py:726-728) ------------------------------------
+// One thread per (class row, 4 columns); the samples of a class are added in index order, so repeated labels give the same bits
+// every run.  Rows of classes absent from the batch are written as zeros (left alone when accumulating).
+__global__ __launch_bounds__(256) void label_emb_bwd_kernel(const float* __restrict__ d_emb, const long long* __restrict__ y, int n,
+                                                            int emb, float* __restrict__ dw, int accumulate) {
+  const int k = blockIdx.x, j = (blockIdx.y * blockDim.x + threadIdx.x) * 4;
+  if (j >= emb) return;
+  float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+  bool hit = false;
+  for (int i = 0; i < n; ++i) {
+    if (y[i] != k) continue;
+    const float4 v = ld4(d_emb + (long long)i * emb + j);
+    s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+    hit = true;
+  }
+  float* d = dw + (long long)k * emb + j;
+  if (accumulate) {
+    if (!hit) return;
+    const float4 old = ld4(d);
+    s.x += old.x; s.y += old.y; s.z += old.z; s.w += old.w;
+  }
+  *reinterpret_cast<float4*>(d) = s;
+}
+
+// ---- avg_pool2d(2, 2) backward: dx[n][2y + i][2x + j][c] (+)= 0.25 dy[n][y][x][c]  (ResBlock(down=True), openaimodel.py:143-160)
+__global__ __launch_bounds__(256) void avgpool2_bwd_kernel(const float* __restrict__ dy, float* __restrict__ dx, int h, int w, int C,
+                                                           int accumulate, long long total4) {
+  const int c4n = C >> 2;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total4; i += (long long)gridDim.x * blockDim.x) {
+    const int c = (int)(i % c4n) * 4;
+    const long long pix = i / c4n;
+    const int xx = (int)(pix % w);
+    const long long t = pix / w;
+    const int yy = (int)(t % h);
+    const long long n = t / h;
+    const float4 s = ld4(dy + pix * C + c);
+    const float4 v = make_float4(0.25f * s.x, 0.25f * s.y, 0.25f * s.z, 0.25f * s.w);
+    const long long big = (((n * 2 * h + 2 * yy) * 2 * w) + 2 * xx) * C + c, row = (long long)2 * w * C;
+    const long long at[4] = {big, big + C, big + row, big + row + C};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      float4 o = v;
+      if (accumulate) {
+        const float4 old = ld4(dx + at[k]);
+        o.x += old.x; o.y += old.y; o.z += old.z; o.w += old.w;
+      }
+      *reinterpret_cast<float4*>(dx + at[k]) = o;
+    }
+  }
+}
+
 // ---- LayerNorm: materialised forward and backward ---------------------------------------------------------
 __global__ __launch_bounds__(256) void ln_apply_kernel(const float* __restrict__ x, const float* __restrict__ stats,
                                                        const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -649,6 +837,58 @@ extern "C" int ldmk_gn_bwd(const float* x0, int c0, const float* x1, int c1, con
 }
 extern "C" long long ldmk_gn_bwd_scratch_elems(int n, int hw, int c, int groups) {
   return (long long)n * ldmk_gn_bwd_chunks(hw) * c * 2 + (long long)n * c * 2 + (long long)n * groups * 2;
+}
+
+extern "C" long long ldmk_gn_film_bwd_scratch_elems(int n, int hw, int c) {
+  return (long long)n * ((hw + GF_PIX - 1) / GF_PIX) * c * 2 + (long long)n * c * 2 + (long long)n * c * 3;
+}
+extern "C" int ldmk_gn_film_bwd(const float* x, const float* dy, const float* coef, const float* mr, const float* gamma,
+                                const float* beta, const float* film, int film_ld, int n, int hw, int c, int groups, float* dx,
+                                int acc_dx, float* dgamma, float* dbeta, int acc_params, float* dfilm, int dfilm_ld,
+                                float* scratch, void* stream) {
+  LDMK_ENTER();
+  LDMK_REQUIRE(x && dy && coef && mr && gamma && beta && film && dx && dgamma && dbeta && dfilm && scratch,
+               "ldmk_gn_film_bwd: null buffer");
+  LDMK_REQUIRE(n > 0 && n <= 65535 && hw > 0 && c > 0 && c % 4 == 0 && groups > 0 && c % groups == 0,
+               "ldmk_gn_film_bwd: bad shape (C%%4==0, C%%groups==0)");
+  LDMK_REQUIRE(film_ld >= 2 * c && dfilm_ld >= 2 * c, "ldmk_gn_film_bwd: (scale | shift) rows are 2 C wide (ld=%d / %d, C=%d)",
+               film_ld, dfilm_ld, c);
+  LDMK_REQUIRE((((uintptr_t)x | (uintptr_t)dy | (uintptr_t)coef | (uintptr_t)dx | (uintptr_t)scratch) & 15) == 0,
+               "ldmk_gn_film_bwd: x, dy, coef, dx and scratch must be 16-byte aligned");
+  const int chunks = (hw + GF_PIX - 1) / GF_PIX;
+  LDMK_REQUIRE(chunks <= 65535, "ldmk_gn_film_bwd: hw too large");
+  float* partial = scratch;                                  // [n][chunks][2][C]
+  float* tot = partial + (long long)n * chunks * c * 2;      // [n][C][2]
+  float* cf = tot + (long long)n * c * 2;                    // [n][3][C]
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(gn_film_bwd_partial_kernel, dim3((c + 63) / 64, chunks, n), dim3(256), 0, st, x, dy, coef, mr, c, hw, groups,
+                     partial);
+  hipLaunchKernelGGL(gn_film_bwd_finalize_kernel, dim3((groups + 3) / 4, n), dim3(256), 0, st, partial, c, hw, chunks, groups, gamma,
+                     beta, mr, film, film_ld, tot, cf, dfilm, dfilm_ld);
+  hipLaunchKernelGGL(gn_bwd_params_kernel, dim3((c + 255) / 256), dim3(256), 0, st, tot, n, c, dgamma, dbeta, acc_params);
+  const long long total4 = (long long)n * hw * (c / 4);
+  hipLaunchKernelGGL(gn_film_bwd_apply_kernel, dim3(grid_for(total4)), dim3(256), 0, st, x, dy, coef, cf, c, hw, dx, acc_dx, total4);
+  return check_launch("ldmk_gn_film_bwd");
+}
+
+extern "C" int ldmk_label_emb_bwd(const float* d_emb, const long long* y, int n, int emb, int classes, float* dw, int accumulate,
+                                  void* stream) {
+  LDMK_ENTER();
+  LDMK_REQUIRE(d_emb && y && dw && n > 0 && emb > 0 && emb % 4 == 0 && classes > 0, "ldmk_label_emb_bwd: bad args (emb%%4==0)");
+  LDMK_REQUIRE((((uintptr_t)d_emb | (uintptr_t)dw) & 15) == 0, "ldmk_label_emb_bwd: d_emb and dw must be 16-byte aligned");
+  const int cols = (emb / 4 + 255) / 256;
+  LDMK_REQUIRE(cols <= 65535, "ldmk_label_emb_bwd: embedding too wide");
+  hipLaunchKernelGGL(label_emb_bwd_kernel, dim3(classes, cols), dim3(256), 0, (hipStream_t)stream, d_emb, y, n, emb, dw, accumulate);
+  return check_launch("ldmk_label_emb_bwd");
+}
+
+extern "C" int ldmk_avgpool2_bwd(const float* dy, float* dx, int n, int h, int w, int c, int accumulate, void* stream) {
+  LDMK_ENTER();
+  LDMK_REQUIRE(dy && dx && dy != dx && n > 0 && h > 0 && w > 0 && c > 0 && c % 4 == 0, "ldmk_avgpool2_bwd: bad args (C%%4==0)");
+  LDMK_REQUIRE((((uintptr_t)dy | (uintptr_t)dx) & 15) == 0, "ldmk_avgpool2_bwd: dy and dx must be 16-byte aligned");
+  const long long total4 = (long long)n * h * w * (c / 4);
+  hipLaunchKernelGGL(avgpool2_bwd_kernel, dim3(grid_for(total4)), dim3(256), 0, (hipStream_t)stream, dy, dx, h, w, c, accumulate, total4);
+  return check_launch("ldmk_avgpool2_bwd");
 }
 
 extern "C" int ldmk_ln_apply(const float* x, const float* stats, const float* gamma, const float* beta, float* y, int rows,

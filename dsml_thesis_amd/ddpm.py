@@ -578,17 +578,30 @@ class LatentDiffusion(_Base):
         """ddpm.py:1014-1047 for the shipped settings (eps-prediction, l2, l_simple_weight 1, fixed logvar 0,
         original_elbo_weight 0): loss = mean((eps_theta(q_sample(x0, t, noise), t, cond) - noise)^2).
         Runs forward AND backward on the HIP kernels; gradients are left in `self.trainer().P.grad` (UNet, packed
-        layout) and `self.trainer().dctx` (w.r.t. the context tokens).  Returns (loss, loss_dict) like the reference;
-        the logged-only `loss_vlb` entry is not computed."""
-        if self.model.conditioning_key not in ("crossattn", "hybrid"):
-            raise NotImplementedError("p_losses: cross-attention conditioned UNets only")
+        layout) and `self.trainer().dctx` (w.r.t. the context tokens; None without a context).  Returns (loss, loss_dict) like
+        the reference; the logged-only `loss_vlb` entry is not computed.
+        `cond` by conditioning_key (DiffusionWrapper, ddpm.py:1404-1423): None -> nothing; 'concat' -> the tensor(s) to concatenate
+        on the channel axis; 'adm' -> class labels (B,) in any form apply_model accepts (y, [y], {"c_crossattn": [y]});
+        'crossattn' / 'hybrid' -> the context tokens."""
+        key = self.model.conditioning_key
         tr = self.trainer()
         noise = torch.randn_like(x_start) if noise is None else noise
-        ctx = self._context_tensor(cond)
+        ctx = y = None
+        if key == "adm":
+            y = cond.get("c_crossattn") if isinstance(cond, dict) else cond
+            y = y[0] if isinstance(y, (list, tuple)) else y
+            assert y is not None and y.dim() == 1, "conditioning_key 'adm': cond = class labels (B,)"
+        elif key == "concat":
+            if c_concat is None:
+                c_concat = cond.get("c_concat") if isinstance(cond, dict) else cond
+        elif key in ("crossattn", "hybrid"):
+            ctx = self._context_tensor(cond)
+        elif key is not None:
+            raise NotImplementedError(f"p_losses: conditioning_key {key!r}")
         if isinstance(c_concat, (list, tuple)):
             c_concat = torch.cat(list(c_concat), 1)
         loss = tr.p_losses(x_start.float(), ctx, t, noise.float(), self.sqrt_alphas_cumprod, self.sqrt_one_minus_alphas_cumprod,
-                           c_concat=c_concat, reduce_world=reduce_world)
+                           c_concat=c_concat, reduce_world=reduce_world, y=y)
         prefix = "train" if self.training else "val"
         return loss, {f"{prefix}_loss_simple": loss, f"{prefix}_loss": loss}
 
@@ -613,10 +626,14 @@ class LatentDiffusion(_Base):
                     c = self.cond_stage_model(cond_batch, training=self.training)
                 except TypeError:
                     c = self.get_learned_conditioning(cond_batch)
-        ctx = self._context_tensor(c)
-        loss, loss_dict = self.p_losses(z, ctx.detach(), t, noise, reduce_world=world_size)   # bucketed all-reduce inside
+        if self.model.conditioning_key in ("crossattn", "hybrid"):
+            ctx = self._context_tensor(c)
+            cond_in = ctx.detach()
+        else:                                   # None / 'concat' / 'adm': no context tokens, nothing to hand back to a conditioner
+            ctx, cond_in = None, c
+        loss, loss_dict = self.p_losses(z, cond_in, t, noise, reduce_world=world_size)   # bucketed all-reduce inside
         tr.adamw_step(lr, weight_decay=weight_decay)
-        if self.cond_stage_trainable and ctx.requires_grad:
+        if self.cond_stage_trainable and ctx is not None and ctx.requires_grad and getattr(tr, "dctx", None) is not None:
             if self._cond_opt is None:
                 self._cond_opt = torch.optim.AdamW(self.cond_stage_model.parameters(), lr=lr, weight_decay=weight_decay)
             for grp in self._cond_opt.param_groups:

@@ -153,6 +153,11 @@ _SIGS = {
     "ldmk_gn_bwd_scratch_elems": (C.c_longlong, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "ldmk_gn_bwd": (C.c_int, [_fp, C.c_int, _fp, C.c_int, _fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp,
                               C.c_int, _fp, C.c_int, _fp, _fp, C.c_int, _fp, _fp]),
+    "ldmk_gn_film_bwd_scratch_elems": (C.c_longlong, [C.c_int, C.c_int, C.c_int]),
+    "ldmk_gn_film_bwd": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp, C.c_int,
+                                   _fp, _fp, C.c_int, _fp, C.c_int, _fp, _fp]),
+    "ldmk_label_emb_bwd": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, _fp, C.c_int, _fp]),
+    "ldmk_avgpool2_bwd": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
     "ldmk_ln_apply": (C.c_int, [_fp, _fp, _fp, _fp, _fp, C.c_int, C.c_int, _fp]),
     "ldmk_ln_bwd_blocks": (C.c_int, [C.c_int]),
     "ldmk_ln_bwd": (C.c_int, [_fp, _fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp, C.c_int, _fp, _fp]),

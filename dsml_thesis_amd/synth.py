@@ -18,6 +18,12 @@ NS_UNET = dict(FR_UNET, image_size=64, in_channels=4, out_channels=4)          #
 # BASELINE configs[0] as worded: a genuinely unconditional LDM -- no SpatialTransformer / context, AttentionBlock with 32-channel heads
 UNCOND_UNET = dict(image_size=64, in_channels=4, out_channels=4, model_channels=160, attention_resolutions=[4, 2, 1],
                    num_res_blocks=2, channel_mult=[1, 2, 4], num_head_channels=32)
+# class-conditional ('adm') UNet with the shipped UNet's widths (160 / 320 / 640 channels, two ResBlocks per level): scale-shift norm,
+# label embedding, AttentionBlock / QKVAttention -- the training benchmark's third model (tools/train_bench.py --unet adm); its
+# GroupNorm shapes are the shipped UNet's, so the FiLM backward can be timed next to the plain one
+ADM_TRAIN_UNET = dict(image_size=32, in_channels=3, out_channels=3, model_channels=160, attention_resolutions=[4, 2, 1],
+                      num_res_blocks=2, channel_mult=[1, 2, 4], num_head_channels=32, use_scale_shift_norm=True, num_classes=1000,
+                      use_new_attention_order=True)
 VQ_F4 = dict(embed_dim=3, n_embed=16384,
              ddconfig=dict(double_z=False, z_channels=3, resolution=128, in_channels=3, out_ch=3, ch=128, ch_mult=[1, 2, 4],
                            num_res_blocks=2, attn_resolutions=[32], dropout=0.0))

@@ -163,14 +163,8 @@ class UNetTrainer:
         self.compute = T.set_compute(compute)
         if unet._packed is None:
             unet.pack_weights()
-        if unet.context_dim is None:
-            raise NotImplementedError("UNetTrainer: spatial-transformer UNets with a context only")
         if not getattr(unet, "_heads32", True):
             raise NotImplementedError("UNetTrainer: attention heads of width 32 only (the flash backward kernels)")
-        if getattr(unet, "use_scale_shift_norm", False) or unet.num_classes is not None:
-            raise NotImplementedError("UNetTrainer: use_scale_shift_norm / num_classes UNets are built for sampling only")
-        if getattr(unet, "resblock_updown", False):
-            raise NotImplementedError("UNetTrainer: resblock_updown UNets are built for sampling only")
         self.unet = unet
         self.dev = next(unet.parameters()).device
         self.P = FlatParams()
@@ -193,6 +187,8 @@ class UNetTrainer:
             add(k, P[k])
         for k in ("time_embed.0.bias", "time_embed.2.bias"):
             add(k, sd[k])
+        if u.num_classes is not None:        # forward order: emb = time_embed(t) + label_emb(y) comes before every block
+            add("label_emb.weight", sd["label_emb.weight"])
         cin = u.in_channels
         assert cin <= 32 and u.out_channels <= 32
         add("in.wpad", ops.pack_conv3x3(F.pad(sd["input_blocks.0.0.weight"], (0, 0, 0, 0, 0, 32 - cin)).contiguous()))
@@ -223,6 +219,14 @@ class UNetTrainer:
                     for k in ("norm1.weight", "norm1.bias", "norm2.weight", "norm2.bias", "norm3.weight", "norm3.bias", "attn1.to_out.0.bias",
                               "attn2.to_out.0.bias", "ff.net.0.proj.bias", "ff.net.2.bias"):
                         add(q + k, sd[q + k])
+            elif m.kind == "attn":
+                # qkv stays in the kernels' own [q | k | v][head][d] column order (unet.pack_attention_block); the legacy-order
+                # permutation is applied / inverted where reference layouts are read or written (reference_grad_layout, ...)
+                add(prefix + "aqkv", P[prefix + "aqkv"])
+                add(prefix + "aqkv_b", P[prefix + "aqkv#b"])
+                add(prefix + "apout", P[prefix + "apout"])
+                for k in ("norm.weight", "norm.bias", "proj_out.bias"):
+                    add(prefix + k, sd[prefix + k])
             elif m.kind in ("down", "up"):
                 add(prefix + "w", P[prefix + "w"])
                 bk = "op.bias" if m.kind == "down" else "conv.bias"
@@ -344,8 +348,9 @@ class UNetTrainer:
             return T.conv3x3_dgrad(dy4, wd, (h, w_), stride=stride)
         return T.conv3x3_dgrad(dy4, wd, (h, w_), stride=stride, out=dx_out, residual=dx_out if dx_acc else None)
 
-    def _gn(self, x0, x1, hw, gname, bname, eps, silu):
-        """GroupNorm(32)(+SiLU) of (the concat of) NHWC tensors, materialised; returns (y2d, saved)."""
+    def _gn(self, x0, x1, hw, gname, bname, eps, silu, film=None):
+        """GroupNorm(32)(+SiLU) of (the concat of) NHWC tensors, materialised; returns (y2d, saved).
+        film: the samples' (scale | shift) rows of a use_scale_shift_norm block, folded into the coefficient planes."""
         p = self.P.p
         n = x0.shape[0]
         c0 = x0.shape[-1]
@@ -356,6 +361,8 @@ class UNetTrainer:
         L.call("ldmk_gn_finalize", pa.data_ptr(), c0, ops._ptr(pb), c1, n, hw, 32, eps, p[gname].data_ptr(), p[bname].data_ptr(),
                coef.data_ptr(), ops.stream())
         mr = T.gn_group_stats(pa, c0, pb, c1, n, hw, 32, eps)
+        if film is not None:
+            T.gn_coef_film_(coef, film)
         y = ops.gn_apply(x0, x1, coef, n, hw, silu=silu)
         return y, (coef, mr)
 
@@ -370,14 +377,31 @@ class UNetTrainer:
 
     # ---- blocks -------------------------------------------------------------------------------------------
     def _res_block(self, prefix, m, x0, x1, h, w, emb_all, d_emb_all, emb_off):
+        """ResBlock (openaimodel.py:176-271).  scale_shift: the block's emb_all slice is (scale | shift), 2 cout wide, and
+        modulates the second GroupNorm instead of adding to conv1's output.  updown ("up" / "down", resblock_updown, :256-261):
+        SiLU(GN(x)) and x go through the parameter-free nearest x2 / avg_pool2d(2, 2) before conv1 and on the skip path."""
         n, hw = x0.shape[0], h * w
+        film = emb_all[:, emb_off:emb_off + 2 * m.cout] if m.scale_shift else None
         y1, s1 = self._gn(x0, x1, hw, prefix + "in_layers.0.weight", prefix + "in_layers.0.bias", 1e-5, True)
         y1 = y1.view(n, h, w, m.cin)
-        bv = emb_all[:, emb_off:emb_off + m.cout]
-        h1 = self._conv(y1, prefix + "c1", prefix + "in_layers.2.bias", batch_vec=bv)
-        y2, s2 = self._gn(h1, None, hw, prefix + "out_layers.0.weight", prefix + "out_layers.0.bias", 1e-5, True)
-        y2 = y2.view(n, h, w, m.cout)
-        if m.cin != m.cout:
+        up = m.updown == "up"
+        if m.updown:
+            assert x1 is None and m.cin == m.cout                # (out_channels == channels, openaimodel.py:573,663)
+            if not up and (h % 2 or w % 2):
+                raise L.LdmkError(f"UNetTrainer(resblock_updown): {h}x{w} grid -- avg_pool2d(2, 2) of an odd grid drops its last "
+                                  "row / column in the reference; use even sizes at every level")
+            oh, ow = (2 * h, 2 * w) if up else (h // 2, w // 2)
+            y1c, xr = T.resample2(y1, up), T.resample2(x0, up)
+        else:
+            oh, ow, y1c, xr = h, w, y1, None
+        ohw = oh * ow
+        bv = None if m.scale_shift else emb_all[:, emb_off:emb_off + m.cout]
+        h1 = self._conv(y1c, prefix + "c1", prefix + "in_layers.2.bias", batch_vec=bv)
+        y2, s2 = self._gn(h1, None, ohw, prefix + "out_layers.0.weight", prefix + "out_layers.0.bias", 1e-5, True, film=film)
+        y2 = y2.view(n, oh, ow, m.cout)
+        if m.updown:
+            out = self._conv(y2, prefix + "c2", prefix + "out_layers.3.bias", residual=xr)
+        elif m.cin != m.cout:
             x0r = x0.reshape(n * hw, -1)
             x1r = None if x1 is None else x1.reshape(n * hw, -1)
             skip = self._lin(x0r, prefix + "skip", prefix + "skip_connection.bias", hw, x1=x1r)
@@ -387,19 +411,33 @@ class UNetTrainer:
             out = self._conv(y2, prefix + "c2", prefix + "out_layers.3.bias", residual=x0)
 
         def bwd():
+            g, p = self.P.g, self.P.p
             dout = self._take(out)
             dy2 = self._conv_bwd(dout, y2, prefix + "c2", prefix + "out_layers.3.bias")
             dh1 = torch.empty_like(h1)
             self.G[h1.data_ptr()] = dh1
-            self._gn_bwd(dy2.view(n * hw, -1), h1, None, hw, s2, prefix + "out_layers.0.weight", prefix + "out_layers.0.bias", True)
-            del dy2
-            T.colsum(dh1.view(n * hw, -1), rows_per_group=hw, out=d_emb_all[:, emb_off:emb_off + m.cout])
-            dy1 = self._conv_bwd(dh1, y1, prefix + "c1", prefix + "in_layers.2.bias")
+            if film is not None:
+                T.gn_film_bwd(h1, dy2.view(n * ohw, -1), s2[0], s2[1], p[prefix + "out_layers.0.weight"],
+                              p[prefix + "out_layers.0.bias"], film, n, ohw, d_emb_all[:, emb_off:emb_off + 2 * m.cout], dx=dh1,
+                              dgamma=g[prefix + "out_layers.0.weight"], dbeta=g[prefix + "out_layers.0.bias"],
+                              acc_params=self.acc_params)
+                del dy2
+            else:
+                self._gn_bwd(dy2.view(n * ohw, -1), h1, None, ohw, s2, prefix + "out_layers.0.weight", prefix + "out_layers.0.bias", True)
+                del dy2
+                T.colsum(dh1.view(n * ohw, -1), rows_per_group=ohw, out=d_emb_all[:, emb_off:emb_off + m.cout])
+            dy1 = self._conv_bwd(dh1, y1c, prefix + "c1", prefix + "in_layers.2.bias")
+            if m.updown:                    # back through the resampling of SiLU(GN(x)): nearest x2 -> 2x2 sums, avg pool -> quarters
+                dy1 = T.sumpool2(dy1) if up else T.avgpool2_bwd(dy1)
             self._gn_bwd(dy1.view(n * hw, -1), x0, x1, hw, s1, prefix + "in_layers.0.weight", prefix + "in_layers.0.bias", True)
             dx0 = self._take(x0)
-            d2 = dout.view(n * hw, -1)
-            if m.cin != m.cout:
-                g, p = self.P.g, self.P.p
+            d2 = dout.view(n * ohw, -1)
+            if m.updown:                    # the skip path took the resampled x
+                if up:
+                    T.sumpool2(dout, out=dx0, accumulate=True)
+                else:
+                    T.avgpool2_bwd(dout, out=dx0, accumulate=True)
+            elif m.cin != m.cout:
                 g[prefix + "skip_connection.bias"].copy_(g[prefix + "out_layers.3.bias"])   # same column sums of dout
                 c0 = x0.shape[-1]
                 T.wgrad_linear(x0.view(n * hw, -1), d2, dw=g[prefix + "skip"][:c0], accumulate=self.acc_params)
@@ -410,6 +448,28 @@ class UNetTrainer:
                     self._lin_dx(d2, p[prefix + "skip"][c0:], out=dx1.view(n * hw, -1), residual=dx1.view(n * hw, -1))
             else:
                 T.axpy_(dx0, dout, 1.0)
+        self._push(bwd, prefix)
+        return out
+
+    def _attn_block(self, prefix, m, x, h, w):
+        """AttentionBlock._forward (openaimodel.py:316-324): GroupNorm32 (eps 1e-5, no activation), qkv projection, self-attention
+        with logits scaled by d^-1/2 (the reference scales q and k by d^-1/4 each), proj_out + the block input."""
+        n, hw = x.shape[0], h * w
+        rows = n * hw
+        xn, sx = self._gn(x, None, hw, prefix + "norm.weight", prefix + "norm.bias", 1e-5, False)
+        qkv = self._lin(xn, prefix + "aqkv", prefix + "aqkv_b", hw)
+        att, lse = T.attn_self_lse(qkv, n, hw, m.heads)
+        out = self._lin(att, prefix + "apout", prefix + "proj_out.bias", hw, residual=x.view(rows, m.ch), stats=True).view(n, h, w, m.ch)
+
+        def bwd():
+            dout = self._take(out).view(rows, m.ch)
+            datt = self._lin_bwd(dout, att, prefix + "apout", prefix + "proj_out.bias")
+            dqkv = T.attn_self_bwd(qkv, att, datt, lse, n, hw, m.heads)
+            del datt
+            dxn = self._lin_bwd(dqkv, xn, prefix + "aqkv", prefix + "aqkv_b")
+            del dqkv
+            self._gn_bwd(dxn, x, None, hw, sx, prefix + "norm.weight", prefix + "norm.bias", False)
+            T.axpy_(self._take(x), dout.view_as(x), 1.0)
         self._push(bwd, prefix)
         return out
 
@@ -527,9 +587,10 @@ class UNetTrainer:
         return out
 
     # ---- whole network -------------------------------------------------------------------------------------
-    def forward(self, x, timesteps, context):
+    def forward(self, x, timesteps, context=None, y=None):
         """x (n,C_in,H,W) fp32 NCHW (already concatenated with any c_concat), timesteps (n,) int64, context (n,L,ctx_dim)
-        (L = 1: the shipped configs' fast path; 1 < L <= 128: general cross-attention).
+        (L = 1: the shipped configs' fast path; 1 < L <= 128: general cross-attention; None for a UNet without spatial
+        transformers), y (n,) class labels of a `num_classes` UNet.
         Returns eps (n,C_out,H,W); records the tape for backward()."""
         u, p, dev = self.unet, self.P.p, self.dev
         T.set_compute(self.compute)
@@ -537,17 +598,23 @@ class UNetTrainer:
             raise L.LdmkError("UNetTrainer.forward: CUDA tensors only (no CPU fallback)")
         activate_bf16_images(self._wt16)
         repack_bf16_weights()            # (bf16 step only) the forward weights' bf16 images follow the optimiser's last update
-        if context is None:
+        assert (y is not None) == (u.num_classes is not None), "must specify y if and only if the model is class-conditional"   # openaimodel.py:720-722
+        if context is None and u.use_spatial_transformer:
             raise L.LdmkError("UNetTrainer.forward: context is required")
-        L_ctx = context.shape[1]
+        if context is not None and not u.use_spatial_transformer:
+            raise L.LdmkError("UNetTrainer.forward: this UNet has no cross-attention (use_spatial_transformer=False): context must be None")
+        L_ctx = 0 if context is None else context.shape[1]
         if L_ctx > 128:
             raise NotImplementedError("UNetTrainer: context longer than 128 tokens")
         n, cin, H, W_ = x.shape
         self.tape, self.G, self.ginit, self._stats = [], {}, set(), {}
         self._dctx_init = False
         mc = u.model_channels
-        ctx = context.reshape(n * L_ctx, u.context_dim).contiguous().float()
-        self.dctx = torch.zeros_like(ctx)
+        if context is None:
+            ctx = self.dctx = None
+        else:
+            ctx = context.reshape(n * L_ctx, u.context_dim).contiguous().float()
+            self.dctx = torch.zeros_like(ctx)
         xp = torch.zeros(n, H, W_, 32, device=dev)
         xp[..., :cin] = x.permute(0, 2, 3, 1)
         # ---- timestep embedding MLP and every ResBlock's emb_layers in one GEMM (K1)
@@ -555,6 +622,10 @@ class UNetTrainer:
         e1 = self._lin(temb, "te0", "time_embed.0.bias", 1)
         s1 = T.silu(e1)
         emb = self._lin(s1, "te2", "time_embed.2.bias", 1)
+        if y is not None:                # emb = time_embed(t_emb) + label_emb(y), openaimodel.py:726-728
+            assert y.shape == (n,)
+            y = y.to(torch.int64).contiguous()
+            T.axpy_(emb, p["label_emb.weight"].index_select(0, y), 1.0)
         s2 = T.silu(emb)
         emb_all = self._lin(s2, "emb_all", "emb_all_b", 1)
         d_emb_all = torch.zeros_like(emb_all)
@@ -562,6 +633,8 @@ class UNetTrainer:
         def bwd_emb():
             ds2 = self._lin_bwd(d_emb_all, s2, "emb_all", "emb_all_b")
             demb = T.silu_bwd(emb, ds2)
+            if y is not None:
+                T.label_emb_bwd(demb, y, self.P.g["label_emb.weight"], accumulate=self.acc_params)
             ds1 = self._lin_bwd(demb, s1, "te2", "time_embed.2.bias")
             de1 = T.silu_bwd(e1, ds1)
             self._lin_bwd(de1, temb, "te0", "time_embed.0.bias", need_dx=False)
@@ -581,6 +654,10 @@ class UNetTrainer:
                 pf = f"{prefix}{j}."
                 if m.kind == "res":
                     cur0 = self._res_block(pf, m, cur0, cur1, h, w, emb_all, d_emb_all, u._emb_off[pf])
+                    if m.updown:
+                        h, w = (2 * h, 2 * w) if m.updown == "up" else (h // 2, w // 2)
+                elif m.kind == "attn":
+                    cur0 = self._attn_block(pf, m, cur0, h, w)
                 elif m.kind == "st":
                     cur0 = self._spatial_tf(pf, m, cur0, h, w, ctx, self.dctx, L_ctx)
                 elif m.kind == "down":
@@ -658,15 +735,16 @@ class UNetTrainer:
         return out
 
     # ---- p_losses / optimizer -------------------------------------------------------------------------------
-    def p_losses(self, x_start, context, t, noise, sqrt_ac, sqrt_1mac, c_concat=None, reduce_world=1):
+    def p_losses(self, x_start, context, t, noise, sqrt_ac, sqrt_1mac, c_concat=None, reduce_world=1, y=None):
         """ddpm.py:1014-1047 with parameterization 'eps', loss_type 'l2', l_simple_weight 1, no learned logvar,
         original_elbo_weight 0: loss = mean((eps_theta(q_sample(x0,t,noise), t, c) - noise)^2); `c_concat` (masked-frame +
-        identity latents of the talking-face model) is concatenated to the noisy latent on the channel axis.  Returns the loss
+        identity latents of the talking-face model) is concatenated to the noisy latent on the channel axis; `context` is None for
+        a UNet without spatial transformers, `y` the class labels of a `num_classes` one.  Returns the loss
         (device scalar) after running forward + backward; gradients are in self.P.grad."""
         x_noisy = T.q_sample(x_start.contiguous(), noise.contiguous(), t, sqrt_ac, sqrt_1mac)
         if c_concat is not None:         # TF DiffusionWrapper: torch.cat([x] + c_concat, dim=1), ddpm2cond.py:1309
             x_noisy = torch.cat([x_noisy, c_concat.float()], 1)
-        self.forward(x_noisy, t, context)
+        self.forward(x_noisy, t, context, y=y)
         n, co, H, W_ = noise.shape
         tgt = torch.zeros_like(self.eps_pad)
         tgt[..., :co] = noise.permute(0, 2, 3, 1)
@@ -729,6 +807,7 @@ class UNetTrainer:
                "o1": "attn1.to_out.0.weight", "q2": "attn2.to_q.weight", "k2": "attn2.to_k.weight",
                "v2": "attn2.to_v.weight", "o2": "attn2.to_out.0.weight", "ff2": "ff.net.2.weight",
                "ff1n": "ff.net.0.proj.weight"}
+        mods = dict(u._walk())
         for name, wp in view.items():
             if name in ("te0", "te2"):
                 out[f"time_embed.{name[2]}.weight"] = wp.t().contiguous()
@@ -736,10 +815,20 @@ class UNetTrainer:
                 for pf, m in u._walk():
                     if m.kind == "res":
                         o = u._emb_off[pf]
+                        wd = 2 * m.cout if m.scale_shift else m.cout         # (scale | shift) with use_scale_shift_norm
                         if name == "emb_all":
-                            out[pf + "emb_layers.1.weight"] = wp[:, o:o + m.cout].t().contiguous()
+                            out[pf + "emb_layers.1.weight"] = wp[:, o:o + wd].t().contiguous()
                         else:
-                            out[pf + "emb_layers.1.bias"] = wp[o:o + m.cout].clone()
+                            out[pf + "emb_layers.1.bias"] = wp[o:o + wd].clone()
+            elif name.endswith(".aqkv"):             # AttentionBlock: kernel column order -> the reference's qkv Conv1d rows
+                b = name[:-4]
+                out[b + "qkv.weight"] = _aqkv_rows(mods[b], wp.t().contiguous(), to_kernel=False).reshape(out[b + "qkv.weight"].shape)
+            elif name.endswith(".aqkv_b"):
+                b = name[:-6]
+                out[b + "qkv.bias"] = _aqkv_rows(mods[b], wp, to_kernel=False).clone()
+            elif name.endswith(".apout"):
+                k = name[:-5] + "proj_out.weight"
+                out[k] = unlin(wp, out[k])
             elif name == "in.wpad":
                 out["input_blocks.0.0.weight"] = unconv(wp, 32, wp.shape[1])[:, :u.in_channels].contiguous()
             elif name == "out.wpad":
@@ -783,6 +872,16 @@ class UNetTrainer:
         self.P.grad.mul_(1.0 / world_size)
 
 
+def _aqkv_rows(m, w, to_kernel):
+    """Rows (first axis, 3 ch long) of an AttentionBlock's qkv weight / bias between the reference's order and the kernels' own
+    [q | k | v][head][d].  QKVAttentionLegacy splits the heads first ([head][q | k | v][d], openaimodel.py:366-367);
+    use_new_attention_order (QKVAttention, :379-407) already is the kernels' order."""
+    if m.new_order:
+        return w
+    a, b = (m.heads, 3) if to_kernel else (3, m.heads)
+    return w.reshape(a, b, m.d_head, *w.shape[1:]).transpose(0, 1).reshape(w.shape)
+
+
 def reference_grad_layout(unet, name, grads):
     """The gradient `name` of the flat packed layout, computed from reference-layout gradients `grads`
     (state-dict key -> tensor, e.g. from autograd on the oracle): what tests compare the HIP gradients against."""
@@ -794,6 +893,16 @@ def reference_grad_layout(unet, name, grads):
         return cat([grads[p + "emb_layers.1.weight"] for p, m in unet._walk() if m.kind == "res"], 0).t()
     if name == "emb_all_b":
         return cat([grads[p + "emb_layers.1.bias"] for p, m in unet._walk() if m.kind == "res"], 0)
+    if name.endswith(".aqkv"):
+        b = name[:-4]
+        wgt = grads[b + "qkv.weight"]
+        return _aqkv_rows(dict(unet._walk())[b], wgt.reshape(wgt.shape[0], -1), to_kernel=True).t()
+    if name.endswith(".aqkv_b"):
+        b = name[:-6]
+        return _aqkv_rows(dict(unet._walk())[b], grads[b + "qkv.bias"], to_kernel=True)
+    if name.endswith(".apout"):
+        wgt = grads[name[:-5] + "proj_out.weight"]
+        return wgt.reshape(wgt.shape[0], -1).t()
     if name == "in.wpad":
         return ops.pack_conv3x3(F.pad(grads["input_blocks.0.0.weight"], (0, 0, 0, 0, 0, 32 - unet.in_channels)).contiguous())
     if name == "out.wpad":

@@ -157,6 +157,36 @@ def gn_bwd(x0, x1, dy, coef, mr, gamma, n, hw, groups=32, silu=True, dx0=None, a
     return dx0, dx1, dgamma, dbeta
 
 
+def gn_coef_film_(coef, film):
+    """Fold FiLM into GroupNorm coefficient planes in place: coef [n][2][C], film = the sample rows (scale | shift), [n][>= 2C]."""
+    n, _, c = coef.shape
+    L.call("ldmk_gn_coef_film", _ptr(coef), _ptr(film), film.stride(0), n, c, stream())
+    return coef
+
+
+def gn_film_bwd(x, dy, coef, mr, gamma, beta, film, n, hw, dfilm, groups=32, dx=None, acc_dx=False, dgamma=None, dbeta=None,
+                acc_params=False):
+    """Backward of h = SiLU(GroupNorm(x) (1 + scale) + shift): `coef` are the FiLM-folded planes the forward applied, `film` /
+    `dfilm` the [n][>= 2C] (scale | shift) rows and their gradient (column slices of emb_all / d_emb_all)."""
+    c = x.shape[-1]
+    dev = x.device
+    dx = torch.empty_like(x) if dx is None else dx
+    dgamma = _f32(c, device=dev) if dgamma is None else dgamma
+    dbeta = _f32(c, device=dev) if dbeta is None else dbeta
+    scratch = _f32(L.load().ldmk_gn_film_bwd_scratch_elems(n, hw, c), device=dev)
+    L.call("ldmk_gn_film_bwd", _ptr(x), _ptr(dy), _ptr(coef), _ptr(mr), _ptr(gamma), _ptr(beta), _ptr(film), film.stride(0), n, hw, c,
+           groups, _ptr(dx), 1 if acc_dx else 0, _ptr(dgamma), _ptr(dbeta), 1 if acc_params else 0, _ptr(dfilm), dfilm.stride(0),
+           _ptr(scratch), stream())
+    return dx, dgamma, dbeta
+
+
+def label_emb_bwd(d_emb, y, dw, accumulate=False):
+    """dw[y[i]] (+)= d_emb[i]: d_emb [n][emb] fp32, y [n] int64, dw [classes][emb]."""
+    n, emb = d_emb.shape
+    L.call("ldmk_label_emb_bwd", _ptr(d_emb), _ptr(y), n, emb, dw.shape[0], _ptr(dw), 1 if accumulate else 0, stream())
+    return dw
+
+
 def ln_apply(x2d, stats, gamma, beta, out=None):
     rows, c = x2d.shape
     out = torch.empty_like(x2d) if out is None else out
@@ -211,6 +241,23 @@ def sumpool2(du, out=None, accumulate=False):
     n, h2, w2, c = du.shape
     out = _f32(n, h2 // 2, w2 // 2, c, device=du.device) if out is None else out
     L.call("ldmk_sumpool2", _ptr(du), _ptr(out), n, h2 // 2, w2 // 2, c, 1 if accumulate else 0, stream())
+    return out
+
+
+def resample2(x, up):
+    """The parameter-free resampling of a ResBlock(up=True / down=True), NHWC: nearest x2 or avg_pool2d(2, 2)."""
+    n, h, w, c = x.shape
+    oh, ow = (2 * h, 2 * w) if up else (h // 2, w // 2)
+    out = _f32(n, oh, ow, c, device=x.device)
+    L.call("ldmk_resample2", _ptr(x), _ptr(out), n, min(h, oh), min(w, ow), c, 1 if up else 0, stream())
+    return out
+
+
+def avgpool2_bwd(dy, out=None, accumulate=False):
+    """avg_pool2d(2, 2) backward: dy (n,h,w,c) -> (n,2h,2w,c), every input pixel gets a quarter of its output pixel's gradient."""
+    n, h, w, c = dy.shape
+    out = _f32(n, 2 * h, 2 * w, c, device=dy.device) if out is None else out
+    L.call("ldmk_avgpool2_bwd", _ptr(dy), _ptr(out), n, h, w, c, 1 if accumulate else 0, stream())
     return out
 
 

@@ -593,6 +593,23 @@ long long ldmk_gn_bwd_scratch_elems(int n, int hw, int c, int groups);
 int ldmk_gn_bwd(const float* x0, int c0, const float* x1, int c1, const float* dy, const float* coef, const float* mr,
                 const float* gamma, int n, int hw, int groups, int silu, float* dx0, int acc0, float* dx1, int acc1,
                 float* dgamma, float* dbeta, int acc_params, float* scratch, void* stream);
+/* FiLM GroupNorm backward (use_scale_shift_norm, openaimodel.py:267-271): h = SiLU(GroupNorm(x) (1 + scale) + shift) with
+ * (scale | shift) = film[sample][0..2C) (row stride film_ld).  coef = the FiLM-folded planes the forward applied
+ * (ldmk_gn_finalize then ldmk_gn_coef_film), mr as for ldmk_gn_bwd.  Writes dx (+= with acc_dx), dgamma / dbeta (+= with
+ * acc_params) and the sample's d(scale | shift) into dfilm[sample][0..2C) (row stride dfilm_ld; plain stores).  One source,
+ * C % 4 == 0, 16-byte aligned x / dy / coef / dx / scratch; scratch = ldmk_gn_film_bwd_scratch_elems floats.  Fixed summation
+ * orders, no atomics: bitwise reproducible. */
+long long ldmk_gn_film_bwd_scratch_elems(int n, int hw, int c);
+int ldmk_gn_film_bwd(const float* x, const float* dy, const float* coef, const float* mr, const float* gamma,
+                     const float* beta, const float* film, int film_ld, int n, int hw, int c, int groups, float* dx,
+                     int acc_dx, float* dgamma, float* dbeta, int acc_params, float* dfilm, int dfilm_ld, float* scratch,
+                     void* stream);
+/* label embedding backward (openaimodel.py:726-728): dw[y[i]][:] (+)= d_emb[i][:], y int64 [n], dw [classes][emb]; the samples
+ * of a class are summed in index order (repeated labels: same bits every run); classes absent from the batch get zero rows
+ * (untouched rows when accumulating); emb % 4 == 0.  Labels are NOT checked against `classes`: a label outside [0, classes)
+ * matches no row and its sample is dropped silently -- validate labels before the call (the trainer's forward gather does) */
+int ldmk_label_emb_bwd(const float* d_emb, const long long* y, int n, int emb, int classes, float* dw, int accumulate,
+                       void* stream);
 /* LayerNorm materialised forward / backward (attention.py:203-205); scratch = ldmk_ln_bwd_blocks(rows)*c*2 floats */
 int ldmk_ln_apply(const float* x, const float* stats, const float* gamma, const float* beta, float* y, int rows, int c,
                   void* stream);
@@ -611,6 +628,8 @@ int ldmk_colsum(const float* x, int ldx, int rows_per_group, int groups, int n, 
                 float* scratch, void* stream);
 /* nearest-x2 upsample backward: dx[n][h][w][c] (+)= sum of the 2x2 block of du[n][2h][2w][c] */
 int ldmk_sumpool2(const float* du, float* dx, int n, int h, int w, int c, int accumulate, void* stream);
+/* avg_pool2d(2, 2) backward (ResBlock(down=True)): dx[n][2h][2w][c] (+)= 0.25 * dy[n][h][w][c]; (h, w) is the pooled grid */
+int ldmk_avgpool2_bwd(const float* dy, float* dx, int n, int h, int w, int c, int accumulate, void* stream);
 int ldmk_silu(const float* x, float* y, long long n, void* stream);
 int ldmk_silu_bwd(const float* x, const float* dy, float* dx, long long n, void* stream);
 int ldmk_axpy(float* y, const float* x, float a, long long n, void* stream);
