@@ -58,6 +58,15 @@ def pack_linear(w):
     return out
 
 
+def permute3(x, perm):
+    """x: contiguous 3-d tensor -> x.permute(perm), contiguous (ldmk_permute3)."""
+    _chk(x, "permute3")
+    d0, d1, d2 = x.shape
+    out = torch.empty(x.shape[perm[0]], x.shape[perm[1]], x.shape[perm[2]], device=x.device, dtype=torch.float32)
+    L.call("ldmk_permute3", _ptr(x), _ptr(out), d0, d1, d2, perm[0], perm[1], perm[2], stream())
+    return out
+
+
 def pack_wfrag(wp):
     """[K][N] packed weight -> its MFMA-fragment-order copy for the row GEMM (ldmk_pack_wfrag); None when the shape
     cannot be packed (K % 8 or N % 32)."""
@@ -628,13 +637,33 @@ def attn_self(qkv, n, tokens, heads, out=None, x3=False, presplit=False, h2_flag
     return out
 
 
-def attn_cross(q, k, v, n, tokens, ctx_len, heads, out=None):
-    C_ = heads * 32
+def attn_cross(q, k, v, n, tokens, ctx_len, heads, out=None, d_head=None):
+    """q: [n tokens][ldq], k / v: [n ctx_len][ldkv] (one leading dimension for both), heads side by side; row strides may exceed
+    heads * d.  d_head None: the 32-wide entry point (ldmk_attn_cross); otherwise ldmk_attn_cross_d (32, 40, 64, 80)."""
+    d = 32 if d_head is None else int(d_head)
     if out is None:
-        out = torch.empty(n * tokens, C_, device=q.device, dtype=torch.float32)
-    L.call("ldmk_attn_cross", _ptr(q), q.stride(0), _ptr(k), _ptr(v), k.stride(0), _ptr(out), out.stride(0), n, tokens,
-           ctx_len, heads, 32 ** -0.5, stream())
+        out = torch.empty(n * tokens, heads * d, device=q.device, dtype=torch.float32)
+    if d_head is None:
+        L.call("ldmk_attn_cross", _ptr(q), q.stride(0), _ptr(k), _ptr(v), k.stride(0), _ptr(out), out.stride(0), n, tokens,
+               ctx_len, heads, 32 ** -0.5, stream())
+    else:
+        L.call("ldmk_attn_cross_d", _ptr(q), q.stride(0), _ptr(k), _ptr(v), k.stride(0), _ptr(out), out.stride(0), n, tokens,
+               ctx_len, heads, d, d ** -0.5, stream())
     return out
+
+
+def heads_gather(src, col0, n, tokens, heads, d, dp, out=None):
+    """Token rows src [n tokens][ld], heads side by side from column col0 -> head-major [n heads][tokens][dp], zero-padded."""
+    if out is None:
+        out = torch.empty(n * heads, tokens, dp, device=src.device, dtype=torch.float32)
+    L.call("ldmk_heads_gather", _ptr(src), src.stride(0), col0, _ptr(out), n, tokens, heads, d, dp, stream())
+    return out
+
+
+def heads_scatter_(src, dst, n, tokens, heads, d, dp):
+    """The inverse: head-major src [n heads][tokens][dp] -> the first heads * d columns of the token rows dst [n tokens][ld]."""
+    L.call("ldmk_heads_scatter", _ptr(src), _ptr(dst), dst.stride(0), n, tokens, heads, d, dp, stream())
+    return dst
 
 
 def softmax_rows_(x2d, scale):
@@ -644,13 +673,14 @@ def softmax_rows_(x2d, scale):
 
 
 # ------------------------------------------------------------------------------------------ small ops
-def dense_small(x, wp, bias=None, silu_in=False, out=None):
+def dense_small(x, wp, bias=None, silu_in=False, out=None, form4=False):
+    """form4: request the 16-byte-load form (silu_in bit 1: at most 4 rows, N and ldo multiples of 4, aligned w / bias / out)."""
     rows, K = x.shape
     N = wp.shape[1]
     if out is None:
         out = torch.empty(rows, N, device=x.device, dtype=torch.float32)
     L.call("ldmk_dense_small", _ptr(x), x.stride(0), _ptr(wp), _ptr(bias), _ptr(out), out.stride(0), rows, K, N,
-           1 if silu_in else 0, stream())
+           (1 if silu_in else 0) | (2 if form4 else 0), stream())
     return out
 
 
