@@ -36,8 +36,10 @@ __device__ __forceinline__ bf16x8 pack8(const f32x16& a, int t) {
                   (__bf16)a[8 * t + 4], (__bf16)a[8 * t + 5], (__bf16)a[8 * t + 6], (__bf16)a[8 * t + 7]};
 }
 
-// stage 64 rows x 32 floats of a [rows][ld] fp32 matrix as bf16: R[row][d] (if R) and T[d][row] (if T); rows past the end are 0
-__device__ __forceinline__ void stage_bf16(__bf16* R, __bf16* T, const float* __restrict__ src, long long ld, int r0, int rows, int tid) {
+// stage 64 rows x 32 floats of a [rows][ld] fp32 matrix, times mul, as bf16: R[row][d] (if R) and T[d][row] (if T); rows past the
+// end are 0
+__device__ __forceinline__ void stage_bf16(__bf16* R, __bf16* T, const float* __restrict__ src, long long ld, int r0, int rows, int tid,
+                                           float mul = 1.0f) {
   const int rr = tid >> 3, d4 = (tid & 7) * 4;
   float4 v[2];
 #pragma unroll
@@ -48,7 +50,7 @@ __device__ __forceinline__ void stage_bf16(__bf16* R, __bf16* T, const float* __
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     const int row = rr + 32 * i;
-    const bf16x4 b = {(__bf16)v[i].x, (__bf16)v[i].y, (__bf16)v[i].z, (__bf16)v[i].w};
+    const bf16x4 b = {(__bf16)(v[i].x * mul), (__bf16)(v[i].y * mul), (__bf16)(v[i].z * mul), (__bf16)(v[i].w * mul)};
     if (R) *reinterpret_cast<bf16x4*>(R + row * BA_RS + d4) = b;
     if (T) { T[(d4 + 0) * BA_TS + row] = b[0]; T[(d4 + 1) * BA_TS + row] = b[1]; T[(d4 + 2) * BA_TS + row] = b[2]; T[(d4 + 3) * BA_TS + row] = b[3]; }
   }
@@ -231,7 +233,10 @@ __global__ __launch_bounds__(256) void attn_bf16_dkv_kernel(const float* __restr
   const bool k_valid = k0 + l31 < tokens;
   const int kk = k_valid ? k0 + l31 : 0;
   bf16x8 kf[2], vf[2];
-  frag_rows(kf, base + (long long)kk * ld + C + h * BA_D, half, k_valid ? scale : 0.f);
+  // the scores must be the forward's, whose log-sum-exp is subtracted from them: bf16(scale q) . bf16(k), as in the forward and the
+  // dQ kernel.  (bf16(q) . bf16(scale k) differs by ~2^-9 |s| -- scale is no power of two -- which at peaked logits, |s| ~ 30, put
+  // several percent on every P of dK and dV.)  dK = dS^T (scale Q) then needs no scale at the end.
+  frag_rows(kf, base + (long long)kk * ld + C + h * BA_D, half, k_valid ? 1.f : 0.f);
   frag_rows(vf, base + (long long)kk * ld + 2 * C + h * BA_D, half, k_valid ? 1.f : 0.f);
   f32x16 dk, dv;
 #pragma unroll
@@ -241,7 +246,7 @@ __global__ __launch_bounds__(256) void attn_bf16_dkv_kernel(const float* __restr
   const int ntiles = (tokens + BA_T - 1) / BA_T;
   for (int qt = 0; qt < ntiles; ++qt) {
     __syncthreads();
-    stage_bf16(Qr, Qt, base + h * BA_D, ld, qt * BA_T, tokens, tid);
+    stage_bf16(Qr, Qt, base + h * BA_D, ld, qt * BA_T, tokens, tid, scale);
     stage_bf16(Or, Ot, dbase + h * BA_D, C, qt * BA_T, tokens, tid);
     if (tid < BA_T) {
       const int q = qt * BA_T + tid;
@@ -272,17 +277,37 @@ __global__ __launch_bounds__(256) void attn_bf16_dkv_kernel(const float* __restr
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
         dv = mm(op_cols(Ot, sub, l31, half, t), pack8(sa, t), dv);          // dV^T[d][key] += dO^T P
-        dk = mm(op_cols(Qt, sub, l31, half, t), pack8(da, t), dk);          // dK^T[d][key] += Q^T dS
+        dk = mm(op_cols(Qt, sub, l31, half, t), pack8(da, t), dk);          // dK^T[d][key] += (scale Q)^T dS
       }
     }
   }
   if (!wave_active) return;
   float* obase = dqkv + (long long)b * tokens * ld + h * BA_D;
-  store_rows_bf(Ts[wave], dk, scale, obase + C, ld, k0, tokens, l31, half);
+  store_rows_bf(Ts[wave], dk, 1.0f, obase + C, ld, k0, tokens, l31, half);
   store_rows_bf(Ts[wave], dv, 1.0f, obase + 2 * C, ld, k0, tokens, l31, half);
 }
 
-void attn_rowdot_launch(const float* dout, const float* out, float* dsum, int tokens, int heads, long long total, hipStream_t st);   // attention_bwd.hip
+// D[b][h][q] = sum_d bf16(dO[q][h][d]) * O[q][h][d].  dO is rounded as the matrix cores see it in dP = dO V^T: dS = P o (dP - D)
+// relies on D = sum_j P_j dP_j, and with the unrounded dO the difference (dO - bf16(dO)) . O ~ 2^-9 |dO| |O| stayed in every dS
+// (with one token, where dS is exactly zero, it was all of dQ and dK).  Summed in double: one rounding, below the matrix cores' own.
+__global__ void attn_bf16_rowdot_kernel(const float* __restrict__ dout, const float* __restrict__ out, float* __restrict__ dsum,
+                                        int tokens, int heads, long long total) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  const long long row = i / heads;
+  const int h = (int)(i - row * heads);
+  const long long b = row / tokens;
+  const int q = (int)(row - b * tokens);
+  const float4* a = reinterpret_cast<const float4*>(dout + (row * heads + h) * BA_D);
+  const float4* o = reinterpret_cast<const float4*>(out + (row * heads + h) * BA_D);
+  double s = 0.0;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const float4 x = a[j], y = o[j];
+    s += (double)(float)(__bf16)x.x * y.x + (double)(float)(__bf16)x.y * y.y + (double)(float)(__bf16)x.z * y.z + (double)(float)(__bf16)x.w * y.w;
+  }
+  dsum[(b * heads + h) * tokens + q] = (float)s;
+}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // fp32-ACCURATE self attention on the bf16 matrix cores (the sampling path; LDMK_COMPUTE_BF16X3 of include/ldmk.h applied
@@ -1491,7 +1516,8 @@ extern "C" int ldmk_attn_self_bwd_bf16(const float* qkv, const float* out, const
   LDMK_REQUIRE(qkv && out && dout && lse && dqkv && dsum, "ldmk_attn_self_bwd_bf16: null buffer");
   LDMK_REQUIRE(n > 0 && tokens > 0 && heads > 0 && heads <= 65535 && n <= 65535, "ldmk_attn_self_bwd_bf16: bad shape");
   hipStream_t st = (hipStream_t)stream;
-  attn_rowdot_launch(dout, out, dsum, tokens, heads, (long long)n * tokens * heads, st);
+  const long long total = (long long)n * tokens * heads;
+  hipLaunchKernelGGL(attn_bf16_rowdot_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, dout, out, dsum, tokens, heads, total);
   dim3 grid((tokens + 127) / 128, heads, n);
   hipLaunchKernelGGL(attn_bf16_dq_kernel, grid, dim3(256), 0, st, qkv, dout, lse, dsum, dqkv, tokens, heads, scale);
   hipLaunchKernelGGL(attn_bf16_dkv_kernel, grid, dim3(256), 0, st, qkv, dout, lse, dsum, dqkv, tokens, heads, scale);

@@ -353,9 +353,29 @@ def attn_self_bwd(qkv, out, dout, lse, n, tokens, heads):
     return dqkv
 
 
-def attn_cross_bwd(q, k, v, dout, n, tokens, ctx_len, heads):
-    """Gradients of ldmk_attn_cross: q [n*tokens][C], k / v [n*ctx_len][C], dout [n*tokens][C] -> (dq, dk, dv)."""
-    dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+def _rows_like(t, out, what):
+    """A gradient buffer with exactly t's shape and row stride (the kernels take ONE leading dimension for a tensor and its
+    gradient).  torch.empty_like would return a compact tensor for a column slice of a wider buffer."""
+    if t.dim() != 2 or t.stride(1) != 1 or t.stride(0) < t.shape[1]:
+        raise L.LdmkError(f"attn_cross_bwd: {what} must be 2-D rows with unit column stride and a row stride >= its width "
+                          f"(shape {tuple(t.shape)}, strides {tuple(t.stride())})")
+    if out is None:
+        return torch.empty_strided(t.shape, t.stride(), device=t.device, dtype=t.dtype)
+    if out.shape != t.shape or out.stride() != t.stride() or out.dtype != t.dtype or out.device != t.device:
+        raise L.LdmkError(f"attn_cross_bwd: d{what} must have the shape and strides of {what} "
+                          f"({tuple(out.shape)} / {tuple(out.stride())} vs {tuple(t.shape)} / {tuple(t.stride())})")
+    return out
+
+
+def attn_cross_bwd(q, k, v, dout, n, tokens, ctx_len, heads, dq=None, dk=None, dv=None):
+    """Gradients of ldmk_attn_cross: q [n*tokens][C], k / v [n*ctx_len][C], dout [n*tokens][C] -> (dq, dk, dv).
+    Row strides may exceed C (column slices of wider buffers); every gradient has the row stride of its input, and k and v
+    must share one."""
+    if k.stride(0) != v.stride(0):
+        raise L.LdmkError(f"attn_cross_bwd: k and v must share one row stride ({k.stride(0)} vs {v.stride(0)})")
+    if dout.dim() != 2 or dout.stride(1) != 1 or dout.stride(0) < dout.shape[1]:
+        raise L.LdmkError(f"attn_cross_bwd: dout must be 2-D rows with unit column stride (strides {tuple(dout.stride())})")
+    dq, dk, dv = _rows_like(q, dq, "q"), _rows_like(k, dk, "k"), _rows_like(v, dv, "v")
     scratch = _f32(2 * n * tokens * heads * ctx_len, device=q.device)
     L.call("ldmk_attn_cross_bwd", _ptr(q), q.stride(0), _ptr(k), _ptr(v), k.stride(0), _ptr(dout), dout.stride(0), _ptr(dq),
            _ptr(dk), _ptr(dv), _ptr(scratch), n, tokens, ctx_len, heads, 32 ** -0.5, stream())
