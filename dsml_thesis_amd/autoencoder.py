@@ -221,7 +221,7 @@ class VQModelInterface(nn.Module):
                     P[k] = v.reshape(v.shape[0], v.shape[1]).contiguous()      # narrow NCHW 1x1: [cout][cin]
                 else:
                     P[k] = ops.pack_linear(v)
-        # bf16x3 images of the GEMM weights (LDMK_COMPUTE_BF16X3): used for the shapes igemm_plans_x3.json lists
+        # bf16x3 images of the GEMM weights (LDMK_COMPUTE_BF16X3): used for the shapes the "bf16x3" section of igemm_plans.json lists
         from .engine import split_enabled
         if split_enabled():
             for k in list(P):

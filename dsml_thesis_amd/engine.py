@@ -9,10 +9,12 @@ consumer kernels instead of streaming ~1 GB of fresh HBM lines per step.
 import ctypes as C
 import math
 import os
+from collections import namedtuple
 
 import torch
 
 from . import lib as L
+from . import ops as _ops
 from . import switches
 
 
@@ -196,6 +198,100 @@ def ps_plan(rest, m, h2=False, max_ratio=None, far=False):
     return lookup(sec, rest, m, max_ratio) if max_ratio is not None else choose(sec, rest, m, far)
 
 
+# select_plan's inputs and result.  PlanPolicy: what the OWNER of a launch program decides -- h2_flag: the site's F16X2 range flag
+# word (ArithSites.flag) or None, far: the job is far from every tuned batch (choose).  WeightImages: the operand forms at hand,
+# looked up by the caller -- x3 / h2: the weight's bf16x3 / F16X2 record (ops.WeightImage) or None, w_frag / a_split: the fragment-order
+# weight copy / a pre-split A is set in the args.  PlanDecision -- image: the record to attach or None, refused: a split-arithmetic
+# plan was found but cannot run (the args go back to f32 operands), a_split: the pre-split A survives (bf16x3 LDS-tiled plans only).
+PlanPolicy = namedtuple("PlanPolicy", "h2_flag far")
+WeightImages = namedtuple("WeightImages", "x3 h2 w_frag a_split")
+PlanDecision = namedtuple("PlanDecision", "compute tile_cfg splitk image refused a_split")
+_VIRTUAL_WS = dict(splitk_ws=1, splitk_ws_elems=1 << 40)
+
+
+def _trial(args, **fields):
+    """A private copy of an args struct with trial values filled in: what the legality probes run on."""
+    t = type(args).from_buffer_copy(args)
+    for k, v in fields.items():
+        setattr(t, k, v)
+    return t
+
+
+def select_plan(lib, args, policy, images, scale_m=None, allow_splitk=True, batch_is_samples=True, per_sample=False):
+    """Choose arithmetic, tile shape and K split for a GEMM: a PlanDecision.  A pure function of the problem in `args` (never
+    written), the owner's `policy`, the operand `images` at hand and the plan tables; see Program.plan for the parameters."""
+    pol = real = (args.M, args.batch)
+    sample_batch = per_sample or (args.batch > 1 and batch_is_samples)
+    if scale_m is not None and scale_m[0] != scale_m[1]:
+        if sample_batch:                       # batched GEMM (one problem per sample): the job-wide view has more problems
+            pol = (args.M, max(1, max(1, args.batch) * scale_m[0] // scale_m[1]))
+        else:
+            pol = (max(1, args.M * scale_m[0] // scale_m[1]), args.batch)
+    t = _trial(args, M=pol[0], batch=pol[1])          # the POLICY problem: what the tables and the heuristic are asked about
+
+    def heuristic():          # (planned against a generous virtual scratch; the real one is sized to what was chosen)
+        cfg, sk = C.c_int(0), C.c_int(0)
+        lib.ldmk_igemm_plan(C.byref(_trial(t, **_VIRTUAL_WS) if allow_splitk else t), C.byref(cfg), C.byref(sk))
+        return cfg.value, max(1, sk.value)
+
+    def legal(p):
+        # legal for the POLICY problem first (the row count every shard of the job shares: a tile that only the smaller real
+        # problem could run must not be chosen, or a shard and the whole job would differ), then for the real one
+        for p.M, p.batch in (pol, real):          # (p is a private copy)
+            if lib.ldmk_igemm_check(C.byref(p)) != 0:
+                return False
+        return True
+
+    m, refused = pol[0], False
+    # bf16x3 arithmetic for the shapes measured faster in it (needs the weight's split images; decided on the policy row
+    # count like every plan, so a sample's result does not depend on how the batch is sharded)
+    if (args.compute == L.COMPUTE_F32 and not args.b_trans and not args.raw_slabs and not sample_batch
+            and m > 0 and (x3_table() or h2_table())):
+        h2_flag, far = policy
+        hp = h2_plan(t, m, far) if h2_flag is not None else None       # a plan measured in the F16X2 arithmetic itself
+        xp = hp if hp is not None else x3_plan(t, m, far)
+        if xp is None and h2_flag is not None and args.a_mode == L.A_CONV3X3 and args.K >= H2_CONV_MIN_K:
+            # A 3x3 convolution nobody measured in a split arithmetic (the tables hold the shapes of the B = 16 / 128 jobs; at
+            # other batches the low-resolution convolutions leave the Winograd route and show up as direct ones with
+            # K = 9 C_in of 2880-11520): long-K implicit GEMMs are matrix-bound, where three fp16 MFMAs per product beat eight
+            # f32 ones on every tile -- they take the F16X2 arithmetic on the tile and K split of their f32 plan
+            # (A/B at 64x64x4 B = 2 and 32x32x3 B = 5 / 7: profiles/r05_plan_coverage.txt; LDMK_H2_CONV_RULE=0 turns it off)
+            fp = tuned_plan(t, m, far) or heuristic()
+            if int(fp[0]) in (1, 2, 4, 5):
+                xp = fp
+        if xp is not None:
+            tile, sk = int(xp[0]), int(xp[1])
+            if tile > 6:
+                t.a_split, t.a_split_ld = 0, 0                # the warp-specialised tiles split A themselves
+            # the F16X2 arithmetic (three fp16 products per term, include/ldmk.h) while the owner's range flag is down:
+            # same shapes, the LDS-tiled form of the tile (the warp-specialised 256-row tiles map to 128x160 / 128x128)
+            img = images.h2 if h2_flag is not None and not t.a_split else None
+            if img is not None:
+                tile = {21: 5, 22: 1}.get(tile, tile)
+            else:
+                img = images.x3
+            if img is not None:
+                p = _trial(t, tile_cfg=tile, splitk=sk, **_VIRTUAL_WS)
+                _ops.attach_image(p, img, h2_flag)
+                if legal(p):
+                    return PlanDecision(img.compute, tile, max(1, sk), img, False, bool(t.a_split) and tile <= 6)
+            refused = True
+    # (a batch that is not per sample -- the 16 transform positions of a Winograd convolution -- is part of the plan key)
+    tuned = tuned_plan(t, m, policy.far) if not sample_batch and m > 0 else None
+    if tuned is not None and tuned[0] > 6:
+        # a row-GEMM wave tile (7..12, never splits K) or a slab-GEMM shape (13..20, small row counts): legal only with
+        # the fragment-order weight copy and when the tile divides this problem (per-sample operands need
+        # rows_per_sample % tile rows == 0); else the heuristic decides
+        p = _trial(t, tile_cfg=int(tuned[0]), splitk=1 if tuned[0] <= 12 else int(tuned[1]), **_VIRTUAL_WS)
+        if p.splitk == 1:
+            p.raw_slabs = 0                                     # an unsplit plan writes its output itself
+        if not (images.w_frag and legal(p)):
+            tuned = None
+    cfg, sk = tuned if tuned is not None else heuristic()
+    # (pre-split A belongs to the bf16x3 LDS-tiled plans, returned above)
+    return PlanDecision(args.compute, int(cfg), max(1, int(sk)), None, refused, False)
+
+
 class ArithSites:
     """The F16X2 range flags of a model, one int32 word per SITE.  A site is a group of launches that share split operands -- a
     convolution with its transform / statistics producer, `LN1 -> QKV -> attention -> to_out`, `LN3 -> GEGLU -> ff.net.2` -- named
@@ -248,6 +344,9 @@ class Program:
         self._all = []
         self.inputs = {}
         self.outputs = {}
+        # the F16X2 range flag of the site being emitted (NetBuilder.site) or None; the job is far from every tuned batch (far_from_tuned)
+        self.h2_flag, self.far_plans = None, False
+        self._skws = self._skcnt = self._gnws = None      # shared split-K scratch / arrival counters / row-tiled GroupNorm scratch
 
     # ---- workspace -----------------------------------------------------------------------
     def alloc(self, *shape, dtype=torch.float32):
@@ -271,7 +370,7 @@ class Program:
     def alloc_ps(self, rows, k, batch=1):
         """A pool buffer for a [rows][k] matrix (x batch) in the PS layout (include/ldmk.h): uint8 [batch * ldmk_ps_bytes]; the
         two-plane F16X2 form while the program runs in that arithmetic (h2_flag)."""
-        nb = (self.lib.ldmk_ps_bytes_h2 if getattr(self, "h2_flag", None) is not None else self.lib.ldmk_ps_bytes)(int(rows), int(k))
+        nb = (self.lib.ldmk_ps_bytes_h2 if self.h2_flag is not None else self.lib.ldmk_ps_bytes)(int(rows), int(k))
         assert nb > 0, (rows, k)
         return self.alloc(int(batch) * nb, dtype=torch.uint8)
 
@@ -284,7 +383,7 @@ class Program:
 
     def splitk_workspace(self, elems):
         """One scratch for split-K partial slabs, shared by every GEMM of the program (stream-ordered)."""
-        if getattr(self, "_skws", None) is None or self._skws.numel() < elems:
+        if self._skws is None or self._skws.numel() < elems:
             self._skws = torch.empty(int(elems), device=self.device, dtype=torch.float32)
             self._all.append(self._skws)
             for _, _, a, name in self.calls:          # re-point GEMMs recorded against an older scratch
@@ -295,7 +394,7 @@ class Program:
     def splitk_counters(self, n=16384):
         """Arrival counters of the in-launch split-K combine: zeroed once; every GEMM launch leaves them zeroed, and the
         GEMMs of a program are stream-ordered, so they all share this one array."""
-        if getattr(self, "_skcnt", None) is None:
+        if self._skcnt is None:
             self._skcnt = torch.zeros(n, device=self.device, dtype=torch.int32)
             self._all.append(self._skcnt)
         return self._skcnt
@@ -307,109 +406,23 @@ class Program:
         per_sample: the GEMM is one problem PER SAMPLE (args.batch = samples) also when this call happens to hold one sample: a
         one-sample shard of a job must plan it as the job does -- a batch of problems, never looked up in the tables -- not as a
         plain GEMM with more rows."""
-        m, nbatch = args.M, args.batch
-        sample_batch = per_sample or (nbatch > 1 and batch_is_samples)
-        if scale_m is not None and scale_m[0] != scale_m[1]:
-            if sample_batch:                       # batched GEMM (one problem per sample): the job-wide view has more problems
-                args.batch = max(1, max(1, nbatch) * scale_m[0] // scale_m[1])
-            else:
-                args.M = max(1, m * scale_m[0] // scale_m[1])
-        cfg, sk = C.c_int(0), C.c_int(0)
-        # bf16x3 arithmetic for the shapes measured faster in it (needs the weight's split images; decided on the policy row
-        # count like every plan, so a sample's result does not depend on how the batch is sharded)
-        if (args.compute == L.COMPUTE_F32 and not args.b_trans and not args.raw_slabs and not sample_batch
-                and args.M > 0 and (x3_table() or h2_table())):
-            h2_flag = getattr(self, "h2_flag", None)
-            far = bool(getattr(self, "far_plans", False))      # the job is far from every tuned batch: carry the nearest plan (choose)
-            hp = h2_plan(args, args.M, far) if h2_flag is not None else None       # a plan measured in the F16X2 arithmetic itself
-            xp = hp if hp is not None else x3_plan(args, args.M, far)
-            if xp is None and h2_flag is not None and args.a_mode == L.A_CONV3X3 and args.K >= H2_CONV_MIN_K:
-                # A 3x3 convolution nobody measured in a split arithmetic (the tables hold the shapes of the B = 16 / 128 jobs; at
-                # other batches the low-resolution convolutions leave the Winograd route and show up as direct ones with
-                # K = 9 C_in of 2880-11520): long-K implicit GEMMs are matrix-bound, where three fp16 MFMAs per product beat eight
-                # f32 ones on every tile -- they take the F16X2 arithmetic on the tile and K split of their f32 plan
-                # (A/B at 64x64x4 B = 2 and 32x32x3 B = 5 / 7: profiles/r05_plan_coverage.txt; LDMK_H2_CONV_RULE=0 turns it off)
-                fp = tuned_plan(args, args.M, far)
-                if fp is None:
-                    c_, k_ = C.c_int(0), C.c_int(0)
-                    keep = (args.splitk_ws, args.splitk_ws_elems)
-                    if allow_splitk:
-                        args.splitk_ws, args.splitk_ws_elems = 1, 1 << 40
-                    self.lib.ldmk_igemm_plan(C.byref(args), C.byref(c_), C.byref(k_))
-                    args.splitk_ws, args.splitk_ws_elems = keep
-                    fp = (c_.value, max(1, k_.value))
-                if int(fp[0]) in (1, 2, 4, 5):
-                    xp = (int(fp[0]), int(fp[1]))
-            if xp is not None:
-                from . import ops as _ops
-                saved = (args.M, args.batch, args.tile_cfg, args.splitk, args.splitk_ws, args.splitk_ws_elems)
-                args.M, args.batch = m, nbatch
-                if int(xp[0]) > 6:
-                    args.a_split, args.a_split_ld = 0, 0          # the warp-specialised tiles split A themselves
-                # the F16X2 arithmetic (three fp16 products per term, include/ldmk.h) while the owner's range flag is down:
-                # same shapes, the LDS-tiled form of the tile (the warp-specialised 256-row tiles map to 128x160 / 128x128)
-                ok = h2_flag is not None and not args.a_split and _ops.set_split_h2(args, h2_flag)
-                if ok:
-                    xp = ({21: 5, 22: 1}.get(int(xp[0]), int(xp[0])), xp[1])
-                else:
-                    ok = _ops.set_split(args)
-                if ok:
-                    # legal for the POLICY problem first (the row count every shard of the job shares: a tile that only the
-                    # smaller real problem could run must not be chosen, or a shard and the whole job would differ), then for
-                    # the real one
-                    args.tile_cfg, args.splitk = int(xp[0]), int(xp[1])
-                    args.splitk_ws, args.splitk_ws_elems = 1, 1 << 40
-                    args.M, args.batch = saved[0], saved[1]
-                    ok = self.lib.ldmk_igemm_check(C.byref(args)) == 0
-                    args.M, args.batch = m, nbatch
-                    ok = ok and self.lib.ldmk_igemm_check(C.byref(args)) == 0
-                (args.M, args.batch, args.tile_cfg, args.splitk, args.splitk_ws, args.splitk_ws_elems) = saved
-                if ok:
-                    args.M, args.batch = m, nbatch
-                    args.tile_cfg, args.splitk = int(xp[0]), max(1, int(xp[1]))
-                    args.splitk_ws, args.splitk_ws_elems = 0, 0
-                    if args.tile_cfg > 6:
-                        args.a_split, args.a_split_ld = 0, 0      # the warp-specialised tiles split A themselves
-                    return args.tile_cfg, args.splitk
-                args.compute, args.w_split, args.w_split_ld, args.w_split_bstride = L.COMPUTE_F32, 0, 0, 0
-                args.w_scale_exp, args.range_flag = 0, 0
-        # (a batch that is not per sample -- the 16 transform positions of a Winograd convolution -- is part of the plan key)
-        tuned = tuned_plan(args, args.M, bool(getattr(self, "far_plans", False))) if not sample_batch and args.M > 0 else None
-        if tuned is not None and tuned[0] > 6:
-            # a row-GEMM wave tile (7..12, never splits K) or a slab-GEMM shape (13..20, small row counts): legal only with
-            # the fragment-order weight copy and when the tile divides this problem (per-sample operands need
-            # rows_per_sample % tile rows == 0); else the heuristic decides
-            saved = (args.M, args.batch, args.tile_cfg, args.splitk, args.splitk_ws, args.splitk_ws_elems, args.raw_slabs)
-            args.tile_cfg = int(tuned[0])
-            args.splitk = 1 if tuned[0] <= 12 else int(tuned[1])
-            args.splitk_ws, args.splitk_ws_elems = 1, 1 << 40          # (validated against the real scratch below)
-            if args.splitk == 1:
-                args.raw_slabs = 0                                      # an unsplit plan writes its output itself
-            ok = bool(args.w_frag) and self.lib.ldmk_igemm_check(C.byref(args)) == 0      # ... for the policy problem (see above)
-            args.M, args.batch = m, nbatch
-            if not ok or self.lib.ldmk_igemm_check(C.byref(args)) != 0:                  # ... and for the real one
-                tuned = None
-            (args.M, args.batch, args.tile_cfg, args.splitk, args.splitk_ws, args.splitk_ws_elems, args.raw_slabs) = saved
-        if tuned is not None:
-            cfg.value, sk.value = int(tuned[0]), int(tuned[1])
-        else:
-            if allow_splitk:
-                # plan against a generous virtual scratch, then size the real one to what was chosen
-                args.splitk_ws, args.splitk_ws_elems = 1, 1 << 40
-            self.lib.ldmk_igemm_plan(C.byref(args), C.byref(cfg), C.byref(sk))
-        args.M, args.batch = m, nbatch
-        args.tile_cfg, args.splitk = cfg.value, max(1, sk.value)
-        args.splitk_ws, args.splitk_ws_elems = 0, 0
-        args.a_split, args.a_split_ld = 0, 0          # (pre-split A belongs to the bf16x3 LDS-tiled plans, returned above)
-        return args.tile_cfg, args.splitk
+        images = WeightImages(_ops.split_of(args.w), _ops.split_h2_of(args.w), bool(args.w_frag), bool(args.a_split))
+        d = select_plan(self.lib, args, PlanPolicy(self.h2_flag, bool(self.far_plans)), images, scale_m, allow_splitk,
+                        batch_is_samples, per_sample)
+        args.compute, args.tile_cfg, args.splitk = d.compute, d.tile_cfg, d.splitk
+        args.splitk_ws, args.splitk_ws_elems = 0, 0          # (the caller attaches the real scratch: _attach_splitk / igemm_raw)
+        if d.image is not None:
+            _ops.attach_image(args, d.image, self.h2_flag)
+        elif d.refused:
+            args.w_split, args.w_split_ld, args.w_split_bstride, args.w_scale_exp, args.range_flag = 0, 0, 0, 0, 0
+        if not d.a_split:
+            args.a_split, args.a_split_ld = 0, 0
+        return d.tile_cfg, d.splitk
 
-    def igemm(self, args, scale_m=None, allow_splitk=True, batch_is_samples=True, per_sample=False):
-        """Record a GEMM (planned here, once: see plan()); a split-K plan gets the program's shared scratch and is
-        followed by its reduce launch."""
-        self.plan(args, scale_m, allow_splitk, batch_is_samples, per_sample)
+    def _attach_splitk(self, args):
+        """A split-K plan gets the program's shared scratch (and is followed by its reduce launch)."""
         if args.splitk > 1:
-            need = max(1, args.batch) * args.splitk * args.M * args.N
-            ws = self.splitk_workspace(need)
+            ws = self.splitk_workspace(max(1, args.batch) * args.splitk * args.M * args.N)
             args.splitk_ws, args.splitk_ws_elems = ws.data_ptr(), ws.numel()
             # In-launch combine (each tile's last-arriving workgroup sums the slabs) is built and tested, but OFF: split-K is
             # chosen exactly when a GEMM has few output tiles, so the combine runs on those few workgroups (10 of 256 CUs
@@ -417,10 +430,16 @@ class Program:
             # spreads the same bytes over the whole chip.  Measured A/B (sample-steps/s, reduce launch -> in-launch):
             # first version (one atomic load per element) 476 -> 446 at 64x64x4 B=16, 1657 -> 1231 at 32x32x3, 249 -> 141
             # at B=1; with the loads batched (64 in flight per wave) 1720 -> 1614 at 32x32x3 and 252 -> 249 at B=1.
-            # LDMK_SPLITK_IN_LAUNCH=1 turns it on.
-            if switches.get("LDMK_SPLITK_IN_LAUNCH"):
+            # LDMK_SPLITK_IN_LAUNCH=1 turns it on (for the GEMMs planned here: the pre-split tiles never take it).
+            if switches.get("LDMK_SPLITK_IN_LAUNCH") and not args.a_ps:
                 cnt = self.splitk_counters()
                 args.splitk_counters, args.splitk_counters_len = cnt.data_ptr(), cnt.numel()
+
+    def igemm(self, args, scale_m=None, allow_splitk=True, batch_is_samples=True, per_sample=False):
+        """Record a GEMM (planned here, once: see plan()); a split-K plan gets the program's shared scratch and is
+        followed by its reduce launch."""
+        self.plan(args, scale_m, allow_splitk, batch_is_samples, per_sample)
+        self._attach_splitk(args)
         self.calls.append((self.lib.ldmk_igemm, (C.byref(args),), args, "ldmk_igemm"))
 
     def igemm_ps(self, args, cfg, sk):
@@ -428,9 +447,7 @@ class Program:
         BEFORE it had the producer write the A operand in that layout)."""
         args.tile_cfg, args.splitk = int(cfg), max(1, int(sk))
         assert args.compute in (L.COMPUTE_BF16X3, L.COMPUTE_F16X2)       # (set by ops.make_igemm_args from the form of w_ps)
-        if args.splitk > 1:
-            ws = self.splitk_workspace(max(1, args.batch) * args.splitk * args.M * args.N)
-            args.splitk_ws, args.splitk_ws_elems = ws.data_ptr(), ws.numel()
+        self._attach_splitk(args)
         rc = self.lib.ldmk_igemm_check(C.byref(args))
         if rc != 0:
             L.check(rc, "ldmk_igemm_check (pre-split plan)")
@@ -452,7 +469,7 @@ class Program:
     def post(self, pargs, keep=None):
         need = self.lib.ldmk_post_scratch_elems(C.byref(pargs))
         if need > 0:                                   # row-tiled GroupNorm (large images): one shared, stream-ordered scratch
-            if getattr(self, "_gnws", None) is None or self._gnws.numel() < need:
+            if self._gnws is None or self._gnws.numel() < need:
                 self._gnws = torch.empty(int(need), device=self.device, dtype=torch.float32)
                 self._all.append(self._gnws)
                 for _, _, k, name in self.calls:
@@ -473,14 +490,12 @@ class NetBuilder:
     """Emits the recurring layer patterns of the UNet / VQGAN into a Program (NHWC activations)."""
 
     def __init__(self, pg, n, pin=None, sites=None):
-        from . import ops
-        self.pg, self.n, self.pin, self.ops = pg, n, pin, ops
+        self.pg, self.n, self.pin, self.ops = pg, n, pin, _ops
         self._stats = {}          # tensor data_ptr -> GroupNorm partial records [rows/32][C][3]
         # F16X2 is decided per SITE (ArithSites): inside `with nb.site(name):` the builder's and the program's `h2_flag` are the
         # site's flag word -- or None for a denied site, and outside any site -- and every emitter below reads them there
         self.sites = sites
-        self.h2_flag = getattr(pg, "h2_flag", None)
-        pg.h2_flag = self.h2_flag
+        self.h2_flag = pg.h2_flag
 
     def site(self, name):
         """Context in which launches are emitted in the arithmetic of site `name`: F16X2 with the site's range flag, or -- the
@@ -598,7 +613,6 @@ class NetBuilder:
     WINO_MIN_CIN = int(switches.get("LDMK_WINO_MIN_CIN", "320"))
 
     def winograd_ok(self, cin, h, w):
-        import os
         if switches.get("LDMK_NO_WINOGRAD"):
             return False
         pol_n = self.pin[0] if self.pin else self.n
@@ -674,7 +688,7 @@ class NetBuilder:
         plan = self.ps_query(tiles, cout, cin, batch=16) if (u_ps is not None and c0 % 16 == 0 and c1 % 16 == 0) else None
         if plan is not None:
             V = pg.alloc_ps(tiles, cin, batch=16)
-            hf = getattr(pg, "h2_flag", None)          # (a program in the F16X2 arithmetic: V as two fp16 planes, range-checked)
+            hf = pg.h2_flag          # (a program in the F16X2 arithmetic: V as two fp16 planes, range-checked)
             if hf is not None:
                 pg.add("ldmk_winograd_input_ps_h2", p_(x0), c0, p_(x1), c1, p_(coef), 1, n, h, w, p_(V), p_(hf))
             else:
@@ -709,7 +723,6 @@ class NetBuilder:
         (ops.pack_upconv) given, >= 320 channels, >= UP_MIN_PIXELS low-resolution pixels at the plan-policy batch -- four 2x2-tap phase
         convolutions on the low-resolution input: 4/9 of the multiplications, exact (measured: 898 -> 522 us for 640->640 at
         16x16 -> 32x32, B = 16)."""
-        import os
         pg, n, ops, p_ = self.pg, self.n, self.ops, self.ptr
         c = x.shape[-1]
         pol_n = self.pin[0] if self.pin else n
@@ -723,7 +736,7 @@ class NetBuilder:
         plan = self.ps_query(pix, cout, 4 * c, batch=4) if (w4_ps is not None and c % 16 == 0) else None
         if plan is not None:          # the gather writes its phase operands in the PS layout (csrc/igemm_ps.hip)
             A = pg.alloc_ps(pix, 4 * c, batch=4)
-            hf = getattr(pg, "h2_flag", None)
+            hf = pg.h2_flag
             if hf is not None:
                 pg.add("ldmk_upconv_gather_ps_h2", p_(x), c, n, h, w, p_(A), p_(hf))
             else:
@@ -769,8 +782,8 @@ class NetBuilder:
         if self.pin is not None and self.pin[0] != self.pin[1] and per_sample:
             m = max(1, M * self.pin[0] // self.pin[1])
         # (a program in the F16X2 arithmetic has its own table: its operands are two fp16 planes, not three bf16 ones)
-        return ps_plan(f"{N},{K},{L.A_ROWS},{tf},{epi},{max(1, batch)}", m, h2=getattr(self.pg, "h2_flag", None) is not None,
-                       far=bool(getattr(self.pg, "far_plans", False)))
+        return ps_plan(f"{N},{K},{L.A_ROWS},{tf},{epi},{max(1, batch)}", m, h2=self.pg.h2_flag is not None,
+                       far=self.pg.far_plans)
 
     def lin_ps(self, plan, M, K, a_ps, wp, w_ps, bias, rows_per_sample, out=None, out_ps=None, geglu=False, stats=False, **kw):
         """Linear on a pre-split tile: a_ps = the [M][K] input in the PS layout, w_ps = ops.pack_wps(wp).  `out` None with out_ps
@@ -782,7 +795,7 @@ class NetBuilder:
             out = pg.alloc(M, ncol)
         a = ops.make_igemm_args(M, N, K, None, K, wp, out, ncol, rows_per_sample, bias=bias,
                                 epi=L.EPI_GEGLU if geglu else L.EPI_NONE, a_ps=a_ps, w_ps=w_ps, out_ps=out_ps,
-                                range_flag=getattr(pg, "h2_flag", None), **kw)
+                                range_flag=pg.h2_flag, **kw)
         if out is not None:
             self._maybe_stats(a, out, rows_per_sample, stats)
         pg.igemm_ps(a, *plan)

@@ -3,8 +3,8 @@ stream provider here; every function enqueues HIP kernels from libldmk.so on tor
 stream and never synchronises.  Activations are NHWC float32 CUDA tensors."""
 import ctypes as C
 import math
-
 import weakref
+from typing import NamedTuple
 
 import torch
 
@@ -194,7 +194,6 @@ _WPS_H2_EXP = {}                  # data_ptr of an F16X2 PS weight image -> (wea
 
 def h2_scale_exp(w):
     """The exponent e with max |2^e w| in [2^13, 2^14) (one host read of max |w|)."""
-    import math
     mx = float(w.abs().max().item())
     e = 13 - math.floor(math.log2(mx)) if mx > 0.0 and math.isfinite(mx) else 0
     return max(-60, min(60, e))
@@ -203,12 +202,8 @@ def h2_scale_exp(w):
 def pack_wps(w, batch=1, h2=False):
     """Packed weights w[K][N] (pack_linear / pack_conv3x3 layout; or [batch][K][N]) -> PS layout of X[N][K] (row = output column):
     the w_ps operand of the pre-split tiles.  h2: the two fp16 planes of 2^e w, e per matrix (remembered for make_igemm_args)."""
-    if batch > 1:
-        assert w.dim() == 3 and w.shape[0] == batch and w.is_contiguous()
-        K, N = w.shape[1], w.shape[2]
-    else:
-        assert w.dim() == 2 and w.is_contiguous()
-        K, N = w.shape
+    assert w.is_contiguous() and ((w.dim() == 3 and w.shape[0] == batch) if batch > 1 else w.dim() == 2)
+    K, N = w.shape[-2:]
     out = ps_empty(N, K, batch, w.device, h2=h2)
     if h2:
         e = h2_scale_exp(w)
@@ -346,35 +341,79 @@ def igemm(args):
     L.call("ldmk_igemm", C.byref(args), stream())
 
 
-# ---- LDMK_COMPUTE_BF16X3: the weights as three bf16 images of their exact split (include/ldmk.h) -------------------
-_SPLIT = {}          # data_ptr of a packed fp32 weight [K][N] (or a batch of them) -> (bf16 tensor, ld, batch stride in elements)
+# ---- the weights of the split arithmetics as 16-bit images (include/ldmk.h): LDMK_COMPUTE_BF16X3 = three bf16 images of the exact
+# split of w, LDMK_COMPUTE_F16X2 = two fp16 images of 2^e w
+class WeightImage(NamedTuple):
+    image: torch.Tensor      # [batch][planes][N][ld]
+    ld: int
+    bstride: int             # batch stride in elements
+    src: weakref.ref         # the packed fp32 weight the images were made from ...
+    version: int             # ... and its _version then
+    scale_exp: int           # F16X2: the exponent e (0 for bf16x3)
+    compute: int             # the arithmetic the images are for
+
+
+_IMAGES = {}         # (data_ptr of a packed fp32 weight [K][N] (or a batch of them), arithmetic) -> WeightImage
+
+
+def _pack_image(w, batch, compute):
+    assert w.is_contiguous() and ((w.dim() == 3 and w.shape[0] == batch) if batch > 1 else w.dim() == 2)
+    K, N = w.shape[-2:]
+    ld = (K + 7) // 8 * 8
+    if compute == L.COMPUTE_F16X2:
+        e = h2_scale_exp(w)
+        out = torch.empty(batch, 2, N, ld, device=w.device, dtype=torch.float16)
+        L.call("ldmk_pack_wsplit_h2", _ptr(w), K, N, N, batch, K * N, e, _ptr(out), ld, stream())
+    else:
+        e, out = 0, torch.empty(batch, 3, N, ld, device=w.device, dtype=torch.bfloat16)
+        L.call("ldmk_pack_wsplit", _ptr(w), K, N, N, batch, K * N, _ptr(out), ld, stream())
+    key = (w.data_ptr(), compute)
+    _IMAGES[key] = WeightImage(out, ld, out.shape[1] * N * ld, weakref.ref(w), w._version, e, compute)
+    # the images die with the weight they were made from (a deleted model must give back its ~6 bytes per parameter); the
+    # entry is dropped only if it still is THIS weight's (the allocator may have handed the address to a newer weight).
+    # Packed weights must not be written through raw pointers after this call: only in-place torch writes move _version.
+    weakref.finalize(w, _drop_image, key, out.data_ptr())
+    return out
+
+
+def _drop_image(key, img_ptr):
+    hit = _IMAGES.get(key)
+    if hit is not None and hit.image.data_ptr() == img_ptr:
+        del _IMAGES[key]
+
+
+def image_of(w_ptr, compute):
+    """The registered images of the weight at this address for this arithmetic, or None (also when the weight tensor has since
+    been freed or written in place: its address / contents may no longer be what was split)."""
+    hit = _IMAGES.get((w_ptr, compute))
+    if hit is None:
+        return None
+    src = hit.src()
+    if src is None or src.data_ptr() != w_ptr or src._version != hit.version:
+        del _IMAGES[(w_ptr, compute)]
+        return None
+    return hit
+
+
+def attach_image(a, img, range_flag=None):
+    """Point igemm args at a weight's images and switch them to the images' arithmetic (F16X2: with the launch's range flag)."""
+    a.w_split, a.w_split_ld, a.w_split_bstride = img.image.data_ptr(), img.ld, img.bstride
+    if img.compute == L.COMPUTE_F16X2:
+        a.w_scale_exp, a.range_flag = img.scale_exp, range_flag.data_ptr()
+        a._keep = getattr(a, "_keep", ()) + (range_flag,)
+    a.compute = img.compute
 
 
 def pack_wsplit(w, batch=1):
     """w: [K][N] fp32 (or [batch][K][N]) on the GPU -> bf16 [batch][3][N][ld] (ldmk_pack_wsplit), registered under w's address
     so that make_igemm_args(..., compute=COMPUTE_BF16X3) finds it."""
-    if batch > 1:
-        assert w.dim() == 3 and w.shape[0] == batch and w.is_contiguous()
-        K, N = w.shape[1], w.shape[2]
-    else:
-        assert w.dim() == 2 and w.is_contiguous()
-        K, N = w.shape
-    ld = (K + 7) // 8 * 8
-    out = torch.empty(batch, 3, N, ld, device=w.device, dtype=torch.bfloat16)
-    L.call("ldmk_pack_wsplit", _ptr(w), K, N, N, batch, K * N, _ptr(out), ld, stream())
-    ptr = w.data_ptr()
-    _SPLIT[ptr] = (out, ld, 3 * N * ld, weakref.ref(w), w._version)
-    # the images die with the weight they were made from (a deleted model must give back its ~6 bytes per parameter); the
-    # entry is dropped only if it still is THIS weight's (the allocator may have handed the address to a newer weight).
-    # Packed weights must not be written through raw pointers after this call: only in-place torch writes move _version.
-    weakref.finalize(w, _drop_split, ptr, out.data_ptr())
-    return out
+    return _pack_image(w, batch, L.COMPUTE_BF16X3)
 
 
-def _drop_split(ptr, img_ptr):
-    hit = _SPLIT.get(ptr)
-    if hit is not None and hit[0].data_ptr() == img_ptr:
-        del _SPLIT[ptr]
+def pack_wsplit_h2(w, batch=1):
+    """w: [K][N] fp32 (or [batch][K][N]) on the GPU -> fp16 [batch][2][N][ld] (ldmk_pack_wsplit_h2): the images hi, lo of 2^e w
+    with e chosen so that max |2^e w| lies in [2^13, 2^14) (one host read of max |w| at pack time); registered under w's address."""
+    return _pack_image(w, batch, L.COMPUTE_F16X2)
 
 
 def pack_wbf16t(w):
@@ -389,59 +428,11 @@ def pack_wbf16t(w):
 
 
 def split_of(w_ptr):
-    """The registered split images of the weight at this address, or None (also when the weight tensor has since been freed
-    or written in place: its address / contents may no longer be what was split)."""
-    hit = _SPLIT.get(w_ptr)
-    if hit is None:
-        return None
-    src = hit[3]()
-    if src is None or src.data_ptr() != w_ptr or src._version != hit[4]:
-        del _SPLIT[w_ptr]
-        return None
-    return hit
-
-
-# ---- LDMK_COMPUTE_F16X2: the weights as two fp16 images of 2^e w (include/ldmk.h) ---------------------------------------------
-_SPLIT_H2 = {}       # data_ptr of a packed fp32 weight -> (f16 tensor, ld, batch stride in elements, weakref, version, scale exponent)
-
-
-def pack_wsplit_h2(w, batch=1):
-    """w: [K][N] fp32 (or [batch][K][N]) on the GPU -> fp16 [batch][2][N][ld] (ldmk_pack_wsplit_h2): the images hi, lo of 2^e w
-    with e chosen so that max |2^e w| lies in [2^13, 2^14) (one host read of max |w| at pack time); registered under w's address."""
-    if batch > 1:
-        assert w.dim() == 3 and w.shape[0] == batch and w.is_contiguous()
-        K, N = w.shape[1], w.shape[2]
-    else:
-        assert w.dim() == 2 and w.is_contiguous()
-        K, N = w.shape
-    mx = float(w.abs().max().item())
-    import math
-    e = 13 - math.floor(math.log2(mx)) if mx > 0.0 and math.isfinite(mx) else 0
-    e = max(-60, min(60, e))
-    ld = (K + 7) // 8 * 8
-    out = torch.empty(batch, 2, N, ld, device=w.device, dtype=torch.float16)
-    L.call("ldmk_pack_wsplit_h2", _ptr(w), K, N, N, batch, K * N, e, _ptr(out), ld, stream())
-    ptr = w.data_ptr()
-    _SPLIT_H2[ptr] = (out, ld, 2 * N * ld, weakref.ref(w), w._version, e)
-    weakref.finalize(w, _drop_split_h2, ptr, out.data_ptr())
-    return out
-
-
-def _drop_split_h2(ptr, img_ptr):
-    hit = _SPLIT_H2.get(ptr)
-    if hit is not None and hit[0].data_ptr() == img_ptr:
-        del _SPLIT_H2[ptr]
+    return image_of(w_ptr, L.COMPUTE_BF16X3)
 
 
 def split_h2_of(w_ptr):
-    hit = _SPLIT_H2.get(w_ptr)
-    if hit is None:
-        return None
-    src = hit[3]()
-    if src is None or src.data_ptr() != w_ptr or src._version != hit[4]:
-        del _SPLIT_H2[w_ptr]
-        return None
-    return hit
+    return image_of(w_ptr, L.COMPUTE_F16X2)
 
 
 def set_split_h2(a, range_flag, w_ptr=None):
@@ -449,10 +440,7 @@ def set_split_h2(a, range_flag, w_ptr=None):
     hit = split_h2_of(a.w if w_ptr is None else w_ptr)
     if hit is None or a.b_trans or range_flag is None:
         return False
-    a.w_split, a.w_split_ld, a.w_split_bstride = hit[0].data_ptr(), hit[1], hit[2]
-    a.w_scale_exp, a.range_flag = hit[5], range_flag.data_ptr()
-    a.compute = L.COMPUTE_F16X2
-    a._keep = getattr(a, "_keep", ()) + (range_flag,)
+    attach_image(a, hit, range_flag)
     return True
 
 
@@ -461,8 +449,7 @@ def set_split(a, w_ptr=None):
     hit = split_of(a.w if w_ptr is None else w_ptr)
     if hit is None or a.b_trans:
         return False
-    a.w_split, a.w_split_ld, a.w_split_bstride = hit[0].data_ptr(), hit[1], hit[2]
-    a.compute = L.COMPUTE_BF16X3
+    attach_image(a, hit)
     return True
 
 

@@ -159,7 +159,7 @@ def emit_self_attention(nb_, qkv, att, hw, heads, d_head, att_ps=None, kv_tiles=
     LDMK_SPLIT_BF16=0: the f32 matrix-core kernel."""
     pg, n = nb_.pg, nb_.n
     scale = d_head ** -0.5
-    h2_flag = getattr(nb_, "h2_flag", None)
+    h2_flag = nb_.h2_flag
     if d_head != 32:
         # Heads that are not 32 wide (reference kwargs num_heads / num_head_channels: openaimodel.py:443-469,542-549; no shipped
         # YAML sets them -- this path exists so that such checkpoints load and meet the oracle, not for speed): per (sample, head)
@@ -259,7 +259,8 @@ def pack_gemm_copies(P, unfolded=False):
         if wf is not None:
             P[k + "#f"] = wf
     # bf16x3 images of the GEMM weights (LDMK_COMPUTE_BF16X3, include/ldmk.h): fp32-accurate products at the bf16 matrix
-    # rate; engine.Program.plan() uses them for the shapes dsml_thesis_amd/igemm_plans_x3.json lists
+    # rate; engine.Program.plan() uses them for the shapes the "bf16x3" / "f16x2" sections of
+    # dsml_thesis_amd/igemm_plans.json list
     if engine_split_enabled():
         for k in list(P):
             tail = k.rsplit(".", 1)[-1]
@@ -319,7 +320,7 @@ def emit_spatial_transformer(nb_, ctx_pg, P, sd, prefix, m, x, h, w, L_ctx, ctx_
     # each other split operands: the QKV epilogue writes the attention's K / V tiles, the attention writes to_out's A operand), `ff` =
     # LN3 -> GEGLU projection -> ff.net.2 [-> proj_out on a pre-split tile], `attn2` (contexts of several tokens), `proj_in`,
     # `proj_out`.  Inside `with nb_.site(...)` nb_.h2_flag is that site's range flag, or None when the site runs in bf16x3.
-    hf = lambda: getattr(nb_, "h2_flag", None)
+    hf = lambda: nb_.h2_flag
     psfx = lambda: "#p2" if hf() is not None else "#p"       # the PS weight copies in the form of the site's arithmetic
 
     kv_state = {"tiles": None}
