@@ -179,6 +179,10 @@ _SIGS = {
     "ldmk_attn_self_bwd_bf16": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_float, _fp]),
     "ldmk_attn_cross_bwd": (C.c_int, [_fp, C.c_int, _fp, _fp, C.c_int, _fp, C.c_int, _fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int,
                                       C.c_int, C.c_float, _fp]),
+    "ldmk_attn_self_lse_d": (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _fp]),
+    "ldmk_attn_self_bwd_d": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _fp]),
+    "ldmk_attn_cross_bwd_d": (C.c_int, [_fp, C.c_int, _fp, _fp, C.c_int, _fp, C.c_int, _fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int,
+                                        C.c_int, C.c_int, C.c_float, _fp]),
     "ldmk_audio_attention_grad_elems": (C.c_longlong, [C.c_int, C.c_int]),
     "ldmk_audio_attention_bwd": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp, _fp]),
     "ldmk_head_permute": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),

@@ -155,16 +155,23 @@ class FlatParams:
 
 
 class UNetTrainer:
-    def __init__(self, unet, compute="f32"):
+    HEAD_WIDTHS = (32, 40, 64, 80)     # per attention site; one UNet may mix them (num_heads = 4: 40 at 160 channels, 80 at 320)
+
+    def __init__(self, unet, compute="f32", want_dx=False):
         """compute: "f32" (the parity path: fp32 matrix cores, bit-exact fmaf-chain products) or "bf16" (BASELINE configs[4]:
         every Conv2d / Linear forward, data-gradient and weight-gradient GEMM rounds its operands to bf16 and runs on
         v_mfma_f32_32x32x16_bf16 with fp32 accumulation; master weights, gradients, AdamW, EMA, normalisations and the
-        attention kernels stay fp32)."""
+        attention kernels stay fp32).  Attention in bf16 mode: heads of 32 run their self attention on the bf16 matrix cores
+        (csrc/attention_bf16.hip); heads of 40, 64 and 80 stay on the fp32 flash kernels (csrc/attention_d.hip), and the
+        short-context cross attention is fp32 at every width.
+        want_dx: backward() also returns the gradient with respect to the network input (differentiable DDIM)."""
         self.compute = T.set_compute(compute)
+        for prefix, m in unet._walk():
+            if m.kind in ("st", "attn") and m.d_head not in self.HEAD_WIDTHS:
+                raise NotImplementedError(f"UNetTrainer: attention heads of width {m.d_head} at {prefix} (built: "
+                                          f"{', '.join(str(w) for w in self.HEAD_WIDTHS)})")
         if unet._packed is None:
             unet.pack_weights()
-        if not getattr(unet, "_heads32", True):
-            raise NotImplementedError("UNetTrainer: attention heads of width 32 only (the flash backward kernels)")
         self.unet = unet
         self.dev = next(unet.parameters()).device
         self.P = FlatParams()
@@ -178,7 +185,7 @@ class UNetTrainer:
         self._stats = {}       # activation data_ptr -> (tensor, GroupNorm partial records emitted by its producer GEMM)
         self._first_off = {}
         self.acc_params = False   # True: backward() adds to P.grad (several passes per step: differentiable DDIM, N2)
-        self.want_dx = False      # True: backward() also returns the gradient w.r.t. the network input
+        self.want_dx = bool(want_dx)   # True: backward() also returns the gradient w.r.t. the network input
 
     # ---- parameters -----------------------------------------------------------------------------------------
     def _collect(self):
@@ -458,13 +465,13 @@ class UNetTrainer:
         rows = n * hw
         xn, sx = self._gn(x, None, hw, prefix + "norm.weight", prefix + "norm.bias", 1e-5, False)
         qkv = self._lin(xn, prefix + "aqkv", prefix + "aqkv_b", hw)
-        att, lse = T.attn_self_lse(qkv, n, hw, m.heads)
+        att, lse = T.attn_self_lse(qkv, n, hw, m.heads, d_head=m.d_head)
         out = self._lin(att, prefix + "apout", prefix + "proj_out.bias", hw, residual=x.view(rows, m.ch), stats=True).view(n, h, w, m.ch)
 
         def bwd():
             dout = self._take(out).view(rows, m.ch)
             datt = self._lin_bwd(dout, att, prefix + "apout", prefix + "proj_out.bias")
-            dqkv = T.attn_self_bwd(qkv, att, datt, lse, n, hw, m.heads)
+            dqkv = T.attn_self_bwd(qkv, att, datt, lse, n, hw, m.heads, d_head=m.d_head)
             del datt
             dxn = self._lin_bwd(dqkv, xn, prefix + "aqkv", prefix + "aqkv_b")
             del dqkv
@@ -487,7 +494,7 @@ class UNetTrainer:
             B["st1"] = ops.ln_stats(hcur)
             B["ln1"] = T.ln_apply(hcur, B["st1"], p[q + "norm1.weight"], p[q + "norm1.bias"])
             B["qkv"] = self._lin(B["ln1"], q + "qkv", None, hw)
-            B["att"], B["lse"] = T.attn_self_lse(B["qkv"], n, hw, m.heads)
+            B["att"], B["lse"] = T.attn_self_lse(B["qkv"], n, hw, m.heads, d_head=m.d_head)
             if L_ctx == 1:
                 # single context token (K11): softmax over one key is 1 -> the block adds to_out(to_v(ctx)) per sample
                 B["v"] = self._lin(ctx, q + "v2", None, 1)
@@ -500,7 +507,7 @@ class UNetTrainer:
                 B["st2"] = ops.ln_stats(B["h1a"])
                 B["ln2"] = T.ln_apply(B["h1a"], B["st2"], p[q + "norm2.weight"], p[q + "norm2.bias"])
                 B["q2"] = self._lin(B["ln2"], q + "q2", None, hw)
-                B["a2"] = ops.attn_cross(B["q2"], B["k2"], B["v2"], n, hw, L_ctx, m.heads)
+                B["a2"] = ops.attn_cross(B["q2"], B["k2"], B["v2"], n, hw, L_ctx, m.heads, d_head=None if m.d_head == 32 else m.d_head)
                 h1 = self._lin(B["a2"], q + "o2", q + "attn2.to_out.0.bias", hw, residual=B["h1a"])
             B["h1"] = h1
             B["st3"] = ops.ln_stats(h1)
@@ -544,7 +551,7 @@ class UNetTrainer:
                 else:
                     # ---- h1 = h1a + to_out2(cross_attn(LN2(h1a), ctx));  h1a = hin + to_out(attn(LN1(hin)))
                     da2 = self._lin_bwd(dh, B["a2"], q + "o2", q + "attn2.to_out.0.bias")
-                    dq2, dk2, dv2 = T.attn_cross_bwd(B["q2"], B["k2"], B["v2"], da2, n, hw, L_ctx, m.heads)
+                    dq2, dk2, dv2 = T.attn_cross_bwd(B["q2"], B["k2"], B["v2"], da2, n, hw, L_ctx, m.heads, d_head=m.d_head)
                     del da2
                     dln2 = self._lin_bwd(dq2, B["ln2"], q + "q2", None)
                     T.ln_bwd(dln2, B["h1a"], B["st2"], p[q + "norm2.weight"], dx=dh, acc_dx=True, dgamma=g[q + "norm2.weight"],
@@ -555,7 +562,7 @@ class UNetTrainer:
                     add_dctx(dk2, q + "k2")
                     add_dctx(dv2, q + "v2")
                     datt = self._lin_bwd(dh, B["att"], q + "o1", q + "attn1.to_out.0.bias")
-                dqkv = T.attn_self_bwd(B["qkv"], B["att"], datt, B["lse"], n, hw, m.heads)   # flash style: no [T][T] matrix
+                dqkv = T.attn_self_bwd(B["qkv"], B["att"], datt, B["lse"], n, hw, m.heads, d_head=m.d_head)   # flash style: no [T][T] matrix
                 del datt
                 dln1 = self._lin_bwd(dqkv, B["ln1"], q + "qkv", None)
                 del dqkv

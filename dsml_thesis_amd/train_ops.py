@@ -334,8 +334,14 @@ def _wgrad_batched(a, dy, out, Z, R, Kw, N):
     wgrad(w)
 
 
-def attn_self_lse(qkv, n, tokens, heads):
-    """Forward attention that also returns the per-row log-sum-exp [n][heads][tokens] (saved for the backward)."""
+def attn_self_lse(qkv, n, tokens, heads, d_head=32):
+    """Forward attention that also returns the per-row log-sum-exp [n][heads][tokens] (saved for the backward).
+    d_head other than 32 (a multiple of 4 in (32, 96]): the fp32 flash kernels of csrc/attention_d.hip, in either compute mode."""
+    if d_head != 32:
+        out = _f32(n * tokens, heads * d_head, device=qkv.device)
+        lse = _f32(n, heads, tokens, device=qkv.device)
+        L.call("ldmk_attn_self_lse_d", _ptr(qkv), _ptr(out), _ptr(lse), n, tokens, heads, int(d_head), d_head ** -0.5, stream())
+        return out, lse
     out = _f32(n * tokens, heads * 32, device=qkv.device)
     lse = _f32(n, heads, tokens, device=qkv.device)
     # bf16 compute mode: Q K^T and P V on the bf16 matrix cores (fp32 softmax / statistics / storage), like the GEMMs
@@ -344,10 +350,18 @@ def attn_self_lse(qkv, n, tokens, heads):
     return out, lse
 
 
-def attn_self_bwd(qkv, out, dout, lse, n, tokens, heads):
-    """d(qkv) of ldmk_attn_self, flash style (probabilities recomputed from lse; any token count)."""
-    dqkv = torch.empty_like(qkv)
+def attn_self_bwd(qkv, out, dout, lse, n, tokens, heads, d_head=32, dqkv=None):
+    """d(qkv) of ldmk_attn_self, flash style (probabilities recomputed from lse; any token count).  dqkv: an optional
+    contiguous result buffer shaped like qkv; every element of it is written."""
+    if dqkv is None:
+        dqkv = torch.empty_like(qkv)
+    elif dqkv.shape != qkv.shape or not dqkv.is_contiguous() or dqkv.dtype != qkv.dtype or dqkv.device != qkv.device:
+        raise L.LdmkError(f"attn_self_bwd: dqkv must be a contiguous buffer shaped like qkv ({tuple(dqkv.shape)} vs {tuple(qkv.shape)})")
     dsum = _f32(n * heads * tokens, device=qkv.device)
+    if d_head != 32:
+        L.call("ldmk_attn_self_bwd_d", _ptr(qkv), _ptr(out), _ptr(dout), _ptr(lse), _ptr(dqkv), _ptr(dsum), n, tokens, heads,
+               int(d_head), d_head ** -0.5, stream())
+        return dqkv
     name = "ldmk_attn_self_bwd_bf16" if COMPUTE == L.COMPUTE_BF16 else "ldmk_attn_self_bwd"
     L.call(name, _ptr(qkv), _ptr(out), _ptr(dout), _ptr(lse), _ptr(dqkv), _ptr(dsum), n, tokens, heads, 32 ** -0.5, stream())
     return dqkv
@@ -367,16 +381,20 @@ def _rows_like(t, out, what):
     return out
 
 
-def attn_cross_bwd(q, k, v, dout, n, tokens, ctx_len, heads, dq=None, dk=None, dv=None):
+def attn_cross_bwd(q, k, v, dout, n, tokens, ctx_len, heads, dq=None, dk=None, dv=None, d_head=32):
     """Gradients of ldmk_attn_cross: q [n*tokens][C], k / v [n*ctx_len][C], dout [n*tokens][C] -> (dq, dk, dv).
     Row strides may exceed C (column slices of wider buffers); every gradient has the row stride of its input, and k and v
-    must share one."""
+    must share one.  d_head other than 32: ldmk_attn_cross_bwd_d (40, 64, 80)."""
     if k.stride(0) != v.stride(0):
         raise L.LdmkError(f"attn_cross_bwd: k and v must share one row stride ({k.stride(0)} vs {v.stride(0)})")
     if dout.dim() != 2 or dout.stride(1) != 1 or dout.stride(0) < dout.shape[1]:
         raise L.LdmkError(f"attn_cross_bwd: dout must be 2-D rows with unit column stride (strides {tuple(dout.stride())})")
     dq, dk, dv = _rows_like(q, dq, "q"), _rows_like(k, dk, "k"), _rows_like(v, dv, "v")
     scratch = _f32(2 * n * tokens * heads * ctx_len, device=q.device)
+    if d_head != 32:
+        L.call("ldmk_attn_cross_bwd_d", _ptr(q), q.stride(0), _ptr(k), _ptr(v), k.stride(0), _ptr(dout), dout.stride(0), _ptr(dq),
+               _ptr(dk), _ptr(dv), _ptr(scratch), n, tokens, ctx_len, heads, int(d_head), d_head ** -0.5, stream())
+        return dq, dk, dv
     L.call("ldmk_attn_cross_bwd", _ptr(q), q.stride(0), _ptr(k), _ptr(v), k.stride(0), _ptr(dout), dout.stride(0), _ptr(dq),
            _ptr(dk), _ptr(dv), _ptr(scratch), n, tokens, ctx_len, heads, 32 ** -0.5, stream())
     return dq, dk, dv

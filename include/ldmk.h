@@ -445,7 +445,8 @@ int ldmk_attn_cross_d(const float* q, int ldq, const float* k, const float* v, i
 /* Self attention for those head widths runs as batched GEMMs (ldmk_igemm, q k^T and p v per (sample, head)) + ldmk_softmax_rows on
  * head-major copies: ldmk_heads_gather copies the heads side by side in token rows src[n tokens][ld] from column col0 to
  * dst[n heads][tokens][dp], each head's d columns zero-padded to dp (a multiple of 32: exact for q k^T); ldmk_heads_scatter is the
- * inverse (first d columns).  The flash kernels (ldmk_attn_self*) stay d_head = 32. */
+ * inverse (first d columns).  That is the sampling path; the d_head = 32 flash kernels (ldmk_attn_self*) stay 32 wide.  The
+ * training step of such heads has flash kernels of its own: ldmk_attn_self_lse_d / ldmk_attn_self_bwd_d below. */
 int ldmk_heads_gather(const float* src, int ld, int col0, float* dst, int n, int tokens, int heads, int d, int dp, void* stream);
 int ldmk_heads_scatter(const float* src, float* dst, int ld, int n, int tokens, int heads, int d, int dp, void* stream);
 int ldmk_softmax_rows(float* x, long long rows, int cols, float scale, void* stream);
@@ -657,6 +658,21 @@ int ldmk_attn_self_bwd_bf16(const float* qkv, const float* out, const float* dou
 int ldmk_attn_cross_bwd(const float* q, int ldq, const float* k, const float* v, int ldkv, const float* dout, int ldo,
                         float* dq, float* dk, float* dv, float* scratch, int n, int tokens, int ctx_len, int heads,
                         float scale, void* stream);
+/* The fp32 flash forward / backward pair and the cross-attention backward for heads that are not 32 wide (csrc/attention_d.hip):
+ * qkv rows [n*tokens][3*C] = (q | k | v) with C = heads * d_head, a head's columns starting at h * d_head.  d_head is a multiple
+ * of 4 with 32 < d_head <= 96 (32 keeps its own entry points above); any tokens >= 1.  Arithmetic as ldmk_attn_self_lse /
+ * ldmk_attn_self_bwd (v_mfma_f32_32x32x2f32, fp32 softmax, log-sum-exp and D; no atomics, bitwise reproducible, a sample's rows
+ * do not depend on the batch); the head width is padded to 64 or 96 inside the kernels, the padding is masked to zero in the
+ * loads and never stored.  lse [n][heads][tokens]; dsum = scratch of n*heads*tokens floats. */
+int ldmk_attn_self_lse_d(const float* qkv, float* out, float* lse, int n, int tokens, int heads, int d_head, float scale,
+                         void* stream);
+int ldmk_attn_self_bwd_d(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv, float* dsum,
+                         int n, int tokens, int heads, int d_head, float scale, void* stream);
+/* Backward of ldmk_attn_cross_d for d_head in {40, 64, 80} (ctx_len <= 128): the two passes, leading dimensions and scratch
+ * (2 * n*tokens*heads*ctx_len floats) of ldmk_attn_cross_bwd. */
+int ldmk_attn_cross_bwd_d(const float* q, int ldq, const float* k, const float* v, int ldkv, const float* dout, int ldo,
+                          float* dq, float* dk, float* dv, float* scratch, int n, int tokens, int ctx_len, int heads,
+                          int d_head, float scale, void* stream);
 /* Backward of ldmk_audio_attention w.r.t. its parameters (the audio features are frozen wav2vec2 outputs): per-sample
  * gradients [n][ldmk_audio_attention_grad_elems(T, dim)] = conv weights (packed [3][cin][cout]) x5, conv biases x5,
  * Linear(T,T) weight, bias; the caller sums over the batch (ldmk_colsum). */

@@ -1,8 +1,10 @@
 """BASELINE config 5 rehearsal on one GPU: UNet training step (p_losses forward + backward + AdamW + EMA), fp32.
 
-  python tools/train_bench.py --batch 16 --latent 32 [--graph] [--steps 10] [--bf16] [--unet shipped|uncond|adm]
+  python tools/train_bench.py --batch 16 --latent 32 [--graph] [--steps 10] [--bf16] [--unet shipped|uncond|adm|heads64]
 --unet: the shipped spatial-transformer UNet (default), `uncond` (BASELINE configs[0]: synth.UNCOND_UNET, AttentionBlocks, no
-context; 64x64x4 latent) or `adm` (synth.ADM_TRAIN_UNET: scale-shift norm + class labels at the shipped widths).
+context; 64x64x4 latent), `adm` (synth.ADM_TRAIN_UNET: scale-shift norm + class labels at the shipped widths) or `heads64` (the
+shipped 64x64x4 UNet, synth.NS_UNET, with num_head_channels = 64: the flash kernels of csrc/attention_d.hip; implies
+--latent 64).
 Reports samples/s and the step's algorithmic TFLOP/s (3x the forward's GEMM FLOPs: forward + data-gradient + weight-
 gradient products; the attention backward recomputes the scores, counted as 2.5x the forward attention FLOPs)."""
 import argparse
@@ -25,8 +27,10 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--graph", action="store_true")
     ap.add_argument("--bf16", action="store_true", help="bf16 GEMM operands (UNetTrainer compute='bf16')")
-    ap.add_argument("--unet", default="shipped", choices=["shipped", "uncond", "adm"])
+    ap.add_argument("--unet", default="shipped", choices=["shipped", "uncond", "adm", "heads64"])
     a = ap.parse_args()
+    if a.unet == "heads64":
+        a.latent = 64
     from dsml_thesis_amd.train import UNetTrainer
     dev = torch.device("cuda", 0)
     if a.unet == "shipped":
@@ -38,8 +42,11 @@ def main():
         from dsml_thesis_amd import schedule, synth
         from dsml_thesis_amd.unet import UNetModel
         ch = 4 if a.latent == 64 else 3
-        ucfg = dict(synth.UNCOND_UNET if a.unet == "uncond" else synth.ADM_TRAIN_UNET, image_size=a.latent, in_channels=ch,
-                    out_channels=ch)
+        if a.unet == "heads64":
+            ucfg = dict(synth.NS_UNET, num_head_channels=64)
+        else:
+            ucfg = dict(synth.UNCOND_UNET if a.unet == "uncond" else synth.ADM_TRAIN_UNET, image_size=a.latent, in_channels=ch,
+                        out_channels=ch)
         unet = UNetModel(**ucfg)
         synth.load_recipe(unet, gain=0.25)
         unet = unet.to(dev).eval()
