@@ -7,7 +7,7 @@
 // Q K^T, P V and the five backward products take bf16 operands (rounded to nearest even) and accumulate in fp32; the
 // softmax, its statistics (log-sum-exp, D = rowsum(dO o O)) and everything stored stay fp32.
 //
-// Algorithm = attention.hip / attention_bwd.hip (flash style, scores recomputed from the forward's log-sum-exp, two
+// Algorithm = attention.hip / attention_train.hip (flash style, scores recomputed from the forward's log-sum-exp, two
 // deterministic backward kernels), re-cut for the 32x32x16 instruction:
 //   * a 32-deep contraction is TWO instructions (k = 16 each) instead of sixteen; operands are 8 bf16 per lane
 //     (lanes 0-31: k 0..7, lanes 32-63: k 8..15);

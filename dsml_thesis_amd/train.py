@@ -162,7 +162,7 @@ class UNetTrainer:
         every Conv2d / Linear forward, data-gradient and weight-gradient GEMM rounds its operands to bf16 and runs on
         v_mfma_f32_32x32x16_bf16 with fp32 accumulation; master weights, gradients, AdamW, EMA, normalisations and the
         attention kernels stay fp32).  Attention in bf16 mode: heads of 32 run their self attention on the bf16 matrix cores
-        (csrc/attention_bf16.hip); heads of 40, 64 and 80 stay on the fp32 flash kernels (csrc/attention_d.hip), and the
+        (csrc/attention_bf16.hip); heads of 40, 64 and 80 stay on the fp32 flash kernels (csrc/attention_train.hip), and the
         short-context cross attention is fp32 at every width.
         want_dx: backward() also returns the gradient with respect to the network input (differentiable DDIM)."""
         self.compute = T.set_compute(compute)

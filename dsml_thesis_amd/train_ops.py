@@ -336,7 +336,7 @@ def _wgrad_batched(a, dy, out, Z, R, Kw, N):
 
 def attn_self_lse(qkv, n, tokens, heads, d_head=32):
     """Forward attention that also returns the per-row log-sum-exp [n][heads][tokens] (saved for the backward).
-    d_head other than 32 (a multiple of 4 in (32, 96]): the fp32 flash kernels of csrc/attention_d.hip, in either compute mode."""
+    d_head other than 32 (a multiple of 4 in (32, 96]): the fp32 flash kernels of csrc/attention_train.hip, in either compute mode."""
     if d_head != 32:
         out = _f32(n * tokens, heads * d_head, device=qkv.device)
         lse = _f32(n, heads, tokens, device=qkv.device)

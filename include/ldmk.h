@@ -658,7 +658,7 @@ int ldmk_attn_self_bwd_bf16(const float* qkv, const float* out, const float* dou
 int ldmk_attn_cross_bwd(const float* q, int ldq, const float* k, const float* v, int ldkv, const float* dout, int ldo,
                         float* dq, float* dk, float* dv, float* scratch, int n, int tokens, int ctx_len, int heads,
                         float scale, void* stream);
-/* The fp32 flash forward / backward pair and the cross-attention backward for heads that are not 32 wide (csrc/attention_d.hip):
+/* The fp32 flash forward / backward pair and the cross-attention backward for heads that are not 32 wide (csrc/attention_train.hip):
  * qkv rows [n*tokens][3*C] = (q | k | v) with C = heads * d_head, a head's columns starting at h * d_head.  d_head is a multiple
  * of 4 with 32 < d_head <= 96 (32 keeps its own entry points above); any tokens >= 1.  Arithmetic as ldmk_attn_self_lse /
  * ldmk_attn_self_bwd (v_mfma_f32_32x32x2f32, fp32 softmax, log-sum-exp and D; no atomics, bitwise reproducible, a sample's rows

@@ -1,4 +1,4 @@
-"""Edge shapes and exact arithmetic of the training-step kernels (csrc/wgrad.hip, attention_bwd.hip, backward.hip and the
+"""Edge shapes and exact arithmetic of the training-step kernels (csrc/wgrad.hip, attention_train.hip, backward.hip and the
 bf16 backward entry points of attention_bf16.hip), below whole-UNet level.
 
 Two kinds of check.  (1) Integer operands in [-2, 2]: every product and partial sum is an integer far below 2^24 (and, for

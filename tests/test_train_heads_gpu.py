@@ -1,4 +1,4 @@
-"""GPU: training UNets whose attention heads are not 32 channels wide (csrc/attention_d.hip: ldmk_attn_self_lse_d,
+"""GPU: training UNets whose attention heads are not 32 channels wide (csrc/attention_train.hip: ldmk_attn_self_lse_d,
 ldmk_attn_self_bwd_d, ldmk_attn_cross_bwd_d) -- the kernels on their own at the tile edges, then whole-network gradients of
 `p_losses` for H40_UNET (heads of 40 and 80), H64_UNET and AttentionBlock UNets with heads of 64.
 

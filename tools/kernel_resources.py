@@ -3,13 +3,15 @@
 
     python tools/kernel_resources.py --base ../parent-worktree [--out profiles/NAME.txt] [--jobs 8]
 
-Compiles every entry of build.SOURCES of both trees (the tree this script lives in, and --base) to gfx950 device assembly with
-build.py's own flags (per-file EXTRA_FLAGS included) plus `--offload-device-only -S`, then prints a two-column table: for
-every kernel symbol the metadata fields that decide occupancy, the instruction count of its body, and whether the two
-instruction streams are the same text.  No GPU needed.  Exit status 1 when the symbol sets or any metadata field differ.
+Compiles every entry of build.SOURCES of both trees (the tree this script lives in, and --base; each tree's own list, so a
+source file may exist in one of them only) to gfx950 device assembly with build.py's flags (per-file EXTRA_FLAGS included)
+plus `--offload-device-only -S`, then prints a two-column table: for every kernel symbol the metadata fields that decide
+occupancy, the instruction count of its body, and whether the two instruction streams are the same text.  No GPU needed.
+Exit status 1 when the symbol sets or any metadata field differ.
 A stand-alone probe: nothing imports it.
 """
 import argparse
+import ast
 import hashlib
 import os
 import re
@@ -26,18 +28,27 @@ from dsml_thesis_amd import build  # noqa: E402  (flags and source list only)
 FIELDS = (".vgpr_count", ".agpr_count", ".private_segment_fixed_size", ".group_segment_fixed_size", ".vgpr_spill_count", ".sgpr_spill_count")
 
 
-def compile_tree(root, outdir, jobs):
+def tree_sources(root, only):
+    """(SOURCES, EXTRA_FLAGS) as that tree's own build.py assigns them: a source file may exist in one tree only"""
+    mod = ast.parse(open(os.path.join(root, "dsml_thesis_amd", "build.py")).read())
+    lit = {n.targets[0].id: ast.literal_eval(n.value) for n in mod.body
+           if isinstance(n, ast.Assign) and getattr(n.targets[0], "id", None) in ("SOURCES", "EXTRA_FLAGS")}
+    return [s for s in lit["SOURCES"] if not only or s in only], lit["EXTRA_FLAGS"]
+
+
+def compile_tree(root, outdir, jobs, only):
     csrc = os.path.join(root, "dsml_thesis_amd", "csrc")
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    sources, extra = tree_sources(root, only)
 
     def one(src):
         out = os.path.join(outdir, src.replace(".hip", ".s"))
-        cmd = [hipcc] + build.FLAGS + build.EXTRA_FLAGS.get(src, []) + ["--offload-device-only", "-S", os.path.join(csrc, src), "-o", out]
+        cmd = [hipcc] + build.FLAGS + extra.get(src, []) + ["--offload-device-only", "-S", os.path.join(csrc, src), "-o", out]
         subprocess.check_call(cmd)
-        return out
+        return src, out
 
     with ThreadPoolExecutor(jobs) as ex:
-        return list(ex.map(one, build.SOURCES))
+        return list(ex.map(one, sources))
 
 
 def parse(path):
@@ -68,17 +79,16 @@ def main():
     ap.add_argument("--base", required=True, help="the tree to compare against (a worktree of the parent commit)")
     ap.add_argument("--out", help="also write the table here")
     ap.add_argument("--jobs", type=int, default=8)
-    ap.add_argument("--only", help="comma-separated subset of build.SOURCES (default: all of them)")
+    ap.add_argument("--only", help="comma-separated subset of build.SOURCES of either tree (default: all of them)")
     args = ap.parse_args()
-    if args.only:
-        build.SOURCES = [s for s in build.SOURCES if s in args.only.split(",")]
+    only = args.only.split(",") if args.only else None
     sides = []
     with tempfile.TemporaryDirectory() as tmp:
         for tag, root in (("base", os.path.abspath(args.base)), ("this", ROOT)):
             d = os.path.join(tmp, tag)
             os.makedirs(d)
             per_file = {}
-            for src, path in zip(build.SOURCES, compile_tree(root, d, args.jobs)):
+            for src, path in compile_tree(root, d, args.jobs, only):
                 for sym, k in parse(path).items():
                     per_file[(src, sym)] = k
             sides.append(per_file)

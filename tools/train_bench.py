@@ -3,7 +3,7 @@
   python tools/train_bench.py --batch 16 --latent 32 [--graph] [--steps 10] [--bf16] [--unet shipped|uncond|adm|heads64]
 --unet: the shipped spatial-transformer UNet (default), `uncond` (BASELINE configs[0]: synth.UNCOND_UNET, AttentionBlocks, no
 context; 64x64x4 latent), `adm` (synth.ADM_TRAIN_UNET: scale-shift norm + class labels at the shipped widths) or `heads64` (the
-shipped 64x64x4 UNet, synth.NS_UNET, with num_head_channels = 64: the flash kernels of csrc/attention_d.hip; implies
+shipped 64x64x4 UNet, synth.NS_UNET, with num_head_channels = 64: the flash kernels of csrc/attention_train.hip; implies
 --latent 64).
 Reports samples/s and the step's algorithmic TFLOP/s (3x the forward's GEMM FLOPs: forward + data-gradient + weight-
 gradient products; the attention backward recomputes the scores, counted as 2.5x the forward attention FLOPs)."""
