@@ -189,6 +189,11 @@ _SIGS = {
     "ldmk_adamw": (C.c_int, [_fp, _fp, _fp, _fp, C.c_longlong, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
                              C.c_int, _fp]),
     "ldmk_ema": (C.c_int, [_fp, _fp, C.c_longlong, C.c_float, _fp]),
+    # ---- differentiable DDIM update (N2 / talking-face fine-tune)
+    "ldmk_ddim_diff_fwd": (C.c_int, [_fp, C.c_int, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
+                                     C.c_float, C.c_float, C.c_int, _fp]),
+    "ldmk_ddim_diff_bwd": (C.c_int, [_fp, _fp, C.c_int, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
+                                     C.c_float, C.c_int, _fp]),
 }
 # every symbol include/ldmk.h declares (checked by tests/test_abi.py against the header text)
 EXPORTED = [k for k in _SIGS if k not in ("ldmk_igemm_force_config", "ldmk_attn_force_qt")]

@@ -8,7 +8,8 @@ frozen, so the decoder needs data gradients only; the UNet accumulates parameter
 
 `DecoderGrad`   : VQGAN decode with a tape; backward(d image) -> d latent.  Kernels: ldmk_igemm (mirrored-tap weights,
                   b_trans), ldmk_gn_bwd, batched GEMMs + ldmk_softmax_bwd_rows for the single-head AttnBlock.
-`DifferentiableDDIM`: S steps of x_{i-1} = c1*x_i + c2*eps_theta(x_i) (eta = 0) through `UNetTrainer` passes.
+`DifferentiableDDIM`: S steps of x_{i-1} = cx*x_i + ce*eps_theta(x_i) + sigma*z_i through `UNetTrainer` passes; the
+                  update and its transpose are one launch each (ldmk_ddim_diff_fwd / ldmk_ddim_diff_bwd).
 """
 import torch
 import torch.nn.functional as F
@@ -210,58 +211,128 @@ def lincomb(terms):
     return out
 
 
+def ddim_diff_fwd(x, eps, cx, ce, sigma=0.0, noise=None, scale=1.0, out=None):
+    """One differentiable DDIM update on the device (ldmk_ddim_diff_fwd): x_prev = cx*x + ce*e + sigma*noise with
+    e = eps, or (1-scale)*e_u + scale*e_c when eps holds the 2n rows [uncond; cond].  x: (n,Cx,H,W) NCHW whose channels
+    [0,C) are the latent (C = eps.shape[1]); out: None -> a new (n,C,H,W), or an NCHW buffer with >= C channels whose
+    first C are written (it may be x itself: the network-input buffer of the channel-concat model)."""
+    n, xc, H, W_ = x.shape
+    C = eps.shape[1]
+    guided = eps.shape[0] == 2 * n
+    assert eps.shape == ((2 * n if guided else n), C, H, W_) and xc >= C, (tuple(x.shape), tuple(eps.shape))
+    out = torch.empty(n, C, H, W_, device=x.device) if out is None else out
+    assert out.shape[0] == n and out.shape[1] >= C and out.shape[2:] == x.shape[2:]
+    assert noise is None or noise.shape == (n, C, H, W_)
+    for t_ in (x, eps, out) + (() if noise is None else (noise,)):
+        assert t_.is_contiguous() and t_.dtype == torch.float32 and t_.is_cuda
+    L.call("ldmk_ddim_diff_fwd", x.data_ptr(), xc, eps.data_ptr(), None if noise is None else noise.data_ptr(), out.data_ptr(),
+           out.shape[1], n, C, H * W_, float(cx), float(ce), float(sigma), float(scale), int(guided), T.stream())
+    return out
+
+
+def ddim_diff_bwd(dx_prev, dxin, cx, ce, scale=1.0, guided=False, want_dx=True, want_deps=True, cpad=32):
+    """The transpose, one launch between two UNet backward passes (ldmk_ddim_diff_bwd): dx = cx*dx_prev + the first C
+    channels of `dxin` (n or 2n rows, both halves added; None: nothing to add) is written over dx_prev, and the next pass's
+    output gradient ce*dx (rows [ce*(1-scale)*dx; ce*scale*dx] when guided) comes back in the channel-padded NHWC layout
+    of `UNetTrainer.pad_output_grad`.  Returns (dx, deps)."""
+    n, C, H, W_ = dx_prev.shape
+    assert dx_prev.is_contiguous() and dx_prev.dtype == torch.float32 and dx_prev.is_cuda
+    if dxin is not None:
+        assert dxin.is_contiguous() and dxin.dtype == torch.float32 and dxin.shape[1] >= C
+        assert dxin.shape[0] == (2 * n if guided else n) and dxin.shape[2:] == dx_prev.shape[2:], tuple(dxin.shape)
+    deps = torch.empty((2 * n if guided else n), H, W_, cpad, device=dx_prev.device) if want_deps else None
+    L.call("ldmk_ddim_diff_bwd", dx_prev.data_ptr(), None if dxin is None else dxin.data_ptr(), 0 if dxin is None else dxin.shape[1],
+           dx_prev.data_ptr() if want_dx else None, None if deps is None else deps.data_ptr(), cpad, n, C, H * W_, float(cx),
+           float(ce), float(scale), int(guided), T.stream())
+    return dx_prev, deps
+
+
 class DifferentiableDDIM:
-    """`LatentDiffusionCLIP.forward` up to the image (latent_diffclip.py:969-1003) with gradients: eta = 0 DDIM steps
-    (ddim2.py:252-290) with classifier-free guidance by batch doubling, then the differentiable decode."""
+    """The differentiable DDIM walks of the two fine-tuning models, up to the image and back:
+    `LatentDiffusionCLIP.forward` (latent_diffclip.py:969-1003; ddim2.py:252-290, eta = 0, classifier-free guidance by
+    batch doubling) and the talking-face fine-tune (ddpm2condtune.py:1026-1053; ddim2cond.py:251-308, eta = 1, masked-frame
+    + identity latents concatenated on the channel axis), then the differentiable decode.  One `ldmk_ddim_diff_fwd`
+    launch per step, one `ldmk_ddim_diff_bwd` launch between two UNet backward passes."""
 
     def __init__(self, model, trainer=None, decoder=None):
         self.model = model
         self.tr = trainer if trainer is not None else model.trainer()
         self.dec = decoder if decoder is not None else DecoderGrad(model.first_stage_model)
+        self.d_context = None
 
-    def forward(self, x, c, table, timesteps, scale=1.0, uc=None):
-        """x (n,C,H,W) start latent; c / uc (n,1,ctx) condition / null tokens; `table` [S][4] = (a_t, a_prev, sigma,
-        sqrt(1-a_t)) rows as built by schedule.ddim_step_table (sigma must be 0); timesteps (S,) int.  Walks the table
-        from the last row to the first (np.flip(ddim_timesteps)) and returns the decoded image."""
+    def forward(self, x, c, table, timesteps, scale=1.0, uc=None, noise=None, c_concat=None):
+        """x (n,C,H,W) start latent; c / uc (n,L,ctx) condition / null tokens; `table` [S][4] = (a_t, a_prev, sigma,
+        sqrt(1-a_t)) rows as built by schedule.ddim_step_table; timesteps (S,) int.  Walks the table from the last row to
+        the first (np.flip(ddim_timesteps)) and returns the decoded image.
+        noise: the S draws of the stochastic steps in walk order (rows with sigma = 0 ignore theirs); None draws them with
+        torch.randn.  c_concat (n,Cc,H,W): constant channels the UNet sees behind the latent, cat([x, c_concat], 1).
+        Neither carries a gradient."""
         self.passes = []
-        n = x.shape[0]
+        n, C, H, W_ = x.shape
+        S = len(timesteps)
         cfg = uc is not None and scale != 1.0
         tr = self.tr
-        x = x.float()
-        for i in reversed(range(len(timesteps))):
+        cur = x.float().contiguous()
+        if c_concat is not None:               # the network-input buffer: concat channels filled once, latent channels per step
+            buf = torch.empty(n, C + c_concat.shape[1], H, W_, device=x.device)
+            buf[:, :C] = cur
+            buf[:, C:] = c_concat
+            cur = buf
+        ctx = torch.cat([uc, c]) if cfg else c
+        for k, i in enumerate(reversed(range(S))):
             a_t, a_prev, sigma, s1m = (float(v) for v in table[i])
-            assert sigma == 0.0, "differentiable DDIM is deterministic (eta = 0) in the reference's fine-tuning scripts"
-            ts = torch.full((n,), int(timesteps[i]), device=x.device, dtype=torch.long)
-            if cfg:
-                eps2 = tr.forward(torch.cat([x, x]), torch.cat([ts, ts]), torch.cat([uc, c]))
-                e_t = lincomb([(1.0 - scale, eps2[:n]), (scale, eps2[n:])])      # e_u + s*(e_c - e_u)
-            else:
-                e_t = tr.forward(x, ts, c)
-            # x_prev = sqrt(a_prev) * (x - s1m*e)/sqrt(a_t) + sqrt(1 - a_prev) * e   (linear in x and e)
+            ts = torch.full((2 * n if cfg else n,), int(timesteps[i]), device=x.device, dtype=torch.long)
+            eps = tr.forward(torch.cat([cur, cur]) if cfg else cur, ts, ctx)      # cfg rows: [uncond; cond]
+            # x_prev = sqrt(a_prev) * (x - s1m*e)/sqrt(a_t) + sqrt(1 - a_prev - sigma^2) * e + sigma * z   (linear in x, e, z)
             cx = (a_prev / a_t) ** 0.5
-            ce = (1.0 - a_prev) ** 0.5 - cx * s1m
+            ce = (1.0 - a_prev - sigma * sigma) ** 0.5 - cx * s1m
+            z = None
+            if sigma != 0.0:
+                z = (torch.randn(n, C, H, W_, device=x.device) if noise is None else noise[k]).float().contiguous()
             self.passes.append((tr.last_pass, cx, ce, cfg, scale, n))
-            x = lincomb([(cx, x), (ce, e_t)])
-        self.z = x
-        return self.dec.forward(lincomb([(1.0 / float(self.model.scale_factor), x)]))
+            into_buf = c_concat is not None and k < S - 1             # the last step leaves the plain latent
+            cur = ddim_diff_fwd(cur, eps, cx, ce, sigma, z, scale, out=cur if into_buf else None)
+        if cur.shape[1] != C:                  # (no steps at all)
+            cur = cur[:, :C].contiguous()
+        self.z = cur
+        self._ctx_shape = tuple(c.shape)
+        return self.dec.forward(lincomb([(1.0 / float(self.model.scale_factor), cur)]))
 
-    def backward(self, dimg):
-        """Accumulates the UNet parameter gradients of all steps into trainer.P.grad; returns d(loss)/d(x_start)."""
+    def backward(self, dimg, dz=None):
+        """Accumulates the UNet parameter gradients of all steps into trainer.P.grad; returns d(loss)/d(x_start) and leaves
+        d(loss)/d(c), summed over the passes (the cond rows only under guidance), in `self.d_context`.
+        dz: gradient of further loss terms on the final latent `self.z`, added to the decoder's."""
         tr = self.tr
         dx = lincomb([(1.0 / float(self.model.scale_factor), self.dec.backward(dimg))])
+        if dz is not None:
+            T.axpy_(dx, dz.float().contiguous(), 1.0)
         tr.P.grad.zero_()
+        self.d_context = None
         old = (tr.acc_params, tr.want_dx)
         tr.acc_params, tr.want_dx = True, True
         try:
-            for ps, cx, ce, cfg, scale, n in reversed(self.passes):
-                if cfg:
-                    deps = torch.cat([lincomb([(ce * (1.0 - scale), dx)]), lincomb([(ce * scale, dx)])])
-                    dxin = tr.backward(UNetTrainer.pad_output_grad(deps), ps)
-                    dx = lincomb([(cx, dx), (1.0, dxin[:n]), (1.0, dxin[n:])])
-                else:
-                    dxin = tr.backward(UNetTrainer.pad_output_grad(lincomb([(ce, dx)])), ps)
-                    dx = lincomb([(cx, dx), (1.0, dxin)])
+            walk = list(reversed(self.passes))
+            deps = None
+            if walk:
+                _, _, ce, cfg, scale, _ = walk[0]
+                _, deps = ddim_diff_bwd(dx, None, 1.0, ce, scale, cfg, want_dx=False)
+            for k, (ps, cx, _, cfg, scale, n) in enumerate(walk):
+                dxin = tr.backward(deps, ps)
+                if ps["dctx"] is not None:                            # every pass has a buffer of its own
+                    rows = ps["dctx"].shape[0] // (2 if cfg else 1)
+                    d = ps["dctx"][-rows:]
+                    if self.d_context is None:
+                        self.d_context = torch.zeros_like(d)
+                    T.axpy_(self.d_context, d, 1.0)
+                last = k + 1 == len(walk)
+                # dxin has this pass's halves; ce and scale of the output gradient are the next pass's.  One walk has one
+                # guidance setting (forward() fixes cfg and scale for all its steps), which the single `guided` flag relies on
+                _, _, ce_next, cfg_next, scale_next, _ = (None, None, 0.0, cfg, scale, None) if last else walk[k + 1]
+                assert cfg_next == cfg
+                _, deps = ddim_diff_bwd(dx, dxin, cx, ce_next, scale_next, cfg, want_deps=not last)
         finally:
             tr.acc_params, tr.want_dx = old
+        if self.d_context is not None:
+            self.d_context = self.d_context.view(self._ctx_shape)
         self.passes = []
         return dx

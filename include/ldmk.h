@@ -687,6 +687,25 @@ int ldmk_head_permute(const float* src, float* dst, int n, int tokens, int parts
 int ldmk_adamw(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2, float eps,
                float weight_decay, int step, void* stream);
 int ldmk_ema(float* shadow, const float* p, long long n, float one_minus_decay, void* stream);
+/* The differentiable DDIM update (ddim2cond.py:272-308) and its transpose (csrc/ddim_diff.hip); fp32, hw = H*W.
+ * Forward: x holds (n,C,H,W) in channels [0,C) of an NCHW tensor with x_channels >= C channels, eps is (n,C,H,W), or
+ * (2n,C,H,W) = [uncond; cond] when guided; noise is (n,C,H,W) or NULL (then sigma must be 0).  Per element, in this order:
+ *   e   = guided ? fma(scale, e_c, (1 - scale) * e_u) : eps
+ *   t   = noise  ? fma(sigma, noise, cx * x)          : cx * x
+ *   out = fma(ce, e, t)
+ * written to channels [0,C) of an NCHW tensor with out_channels >= C channels (out_channels > C: the network-input buffer
+ * whose other channels hold the concat condition; they are not touched).  out may be x.  Vector loads / stores when every
+ * tensor and stride is 16-byte aligned, a scalar tail for a contiguous size that is no multiple of 4, scalar otherwise.
+ * Backward, one launch between two UNet backward passes of the walk:
+ *   dx   = cx * dx_prev + sum over the halves of dxin[:, :C]   (dxin: (n or 2n, in_channels, H, W) NCHW, or NULL: no sum)
+ *   deps = ce * dx, or under guidance the rows [ce * (1 - scale) * dx ; ce * scale * dx], as (n or 2n, H, W, cpad) NHWC
+ *          with channels >= C written as zeros: the output gradient of the pass that comes next (ce, scale are that pass's)
+ * dx_prev and dx are (n,C,H,W); dx may be dx_prev; dx or deps may be NULL (the launch before the first pass is cx = 1,
+ * dxin = dx = NULL: deps = ce * dx_prev; the launch after the last one has deps = NULL).  cpad % 4 == 0. */
+int ldmk_ddim_diff_fwd(const float* x, int x_channels, const float* eps, const float* noise, float* out, int out_channels,
+                       int n, int C, int hw, float cx, float ce, float sigma, float scale, int guided, void* stream);
+int ldmk_ddim_diff_bwd(const float* dx_prev, const float* dxin, int in_channels, float* dx, float* deps, int cpad, int n, int C,
+                       int hw, float cx, float ce, float scale, int guided, void* stream);
 
 #ifdef __cplusplus
 }
