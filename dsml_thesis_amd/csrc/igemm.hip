@@ -1412,6 +1412,7 @@ static int igemm_entry(const ldmk_igemm_args* args, void* stream, bool launch) {
   LDMK_REQUIRE(a.compute == LDMK_COMPUTE_F32 || a.compute == LDMK_COMPUTE_BF16 || a.compute == LDMK_COMPUTE_BF16X3 || a.compute == LDMK_COMPUTE_F16X2,
                "ldmk_igemm: compute=%d", a.compute);
   const bool ps_tile = a.tile_cfg > kNumCfg + kNumRCfg + kNumSCfg + kNumWCfg;
+  LDMK_REQUIRE(!a.a_ps1 || (ps_tile && a.a_ps), "ldmk_igemm: a_ps1 (second A source) is read by the pre-split tiles only, next to a_ps");
   if (a.compute == LDMK_COMPUTE_BF16X3 && !ps_tile) {
     LDMK_REQUIRE(a.w_split && !a.b_trans && a.w_split_ld >= a.K && a.w_split_ld % 8 == 0,
                  "ldmk_igemm: LDMK_COMPUTE_BF16X3 needs w_split (ldmk_pack_wsplit), b_trans = 0, w_split_ld >= K and a multiple of 8");

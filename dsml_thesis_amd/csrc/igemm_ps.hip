@@ -22,6 +22,11 @@
 // LayerNorm, GEGLU, GroupNorm records) or, TR = true, with the accumulators TRANSPOSED (operands swapped in the MFMA: lane =
 // row, registers = 4 x 4 consecutive columns), which stores float4 rows and can write the result pre-split in the PS layout
 // for the next GEMM (args.out_ps) -- each activation element is then split exactly once, by its producer.
+// Two A sources (args.a_ps1 / a_ps_k0, rows mode): A = [A0 | A1] with A0 = a_ps (K-width a_ps_k0) and A1 = a_ps1 (width K - a_ps_k0),
+// two PS tensors of their own -- a stage's A units take their buffer descriptor and offset from the source its global k-slab falls
+// in (wave-uniform, SGPRs); ring, stage count, vmcnt accounting and the split-K partition (32-deep chunks of ALL of K: a source
+// boundary may lie inside a slice) are those of one source, so the result is bitwise that of a launch on pack([A0 | A1]).  Used by
+// the SpatialTransformer's last block: ff.net.2 and proj_out as one GEMM on [GEGLU output | ff.net.2's residual] (ops.fold_pout).
 #include "ldmk_common.h"
 #include "ldmk_split.h"
 #include "ldmk_epilogue.h"
@@ -382,28 +387,37 @@ __global__ __launch_bounds__(64 * NWM * NWN, 2) void igemm_ps_kernel(const ldmk_
 
   // (dbg, probe runs only -- LDMK_PS_DEBUG: bit 0 = zero-record descriptors: every DMA is issued but dropped by the range check,
   //  no memory traffic; bit 1 = no DMA instructions at all; bit 2 = no matrix instructions.  Results are garbage then.)
-  const u32x4 rs_a = buffer_rsrc(reinterpret_cast<const unsigned char*>(p.a_ps) + (long long)bz * p.a_ps_bstride, (dbg & 1) ? 0u : (unsigned)Mb * (unsigned)Kb * (unsigned)UB);
+  // Two A sources (args.a_ps1): k-slabs [0, Ka0) of A come from a_ps, a PS tensor of its own K-width a_ps_k0, slabs [Ka0, Kb) from
+  // a_ps1 (width K - a_ps_k0) -- the K-concat [A0 | A1] without a tensor that holds it.  One source: Ka0 = Kb, rs_a1 is never read.
+  const int Ka0 = p.a_ps1 ? p.a_ps_k0 / 16 : Kb, Ka1 = Kb - Ka0;
+  const u32x4 rs_a = buffer_rsrc(reinterpret_cast<const unsigned char*>(p.a_ps) + (long long)bz * p.a_ps_bstride, (dbg & 1) ? 0u : (unsigned)Mb * (unsigned)Ka0 * (unsigned)UB);
+  const u32x4 rs_a1 = buffer_rsrc(p.a_ps1 ? p.a_ps1 : p.a_ps, (dbg & 1) ? 0u : (unsigned)Mb * (unsigned)Ka1 * (unsigned)UB);
   const u32x4 rs_b = buffer_rsrc(reinterpret_cast<const unsigned char*>(p.w_ps) + (long long)bz * p.w_ps_bstride, (dbg & 1) ? 0u : (unsigned)Nb * (unsigned)Kb * (unsigned)UB);
-  // this wave's units u = wave + NW i: byte offset of the block's first k-slab (wave-uniform), or PS_OOB for blocks past the edge
-  unsigned ubase[UHI];
+  // this wave's units u = wave + NW i: byte offset of the block's first k-slab (wave-uniform), or PS_OOB for blocks past the edge;
+  // ubase1: the same for an A unit in the second source, so that ubase1 + s UB is the offset of global slab 2 it_begin + s there
+  // (unsigned wrap-around: the sum is only used once that slab is >= Ka0)
+  unsigned ubase[UHI], ubase1[UHI];
 #pragma unroll
   for (int i = 0; i < UHI; ++i) {
     const int u = wave + NW * i;
     const int blk = u < FA ? m0 / 32 + u : n0 / 32 + (u - FA);
     const bool ok = u < U && (u < FA ? blk < Mb : blk < Nb);
-    ubase[i] = ok ? (unsigned)blk * (unsigned)Kb * (unsigned)UB + (unsigned)(2 * it_begin) * (unsigned)UB : PS_OOB;
+    ubase[i] = ok ? (unsigned)blk * (unsigned)(u < FA ? Ka0 : Kb) * (unsigned)UB + (unsigned)(2 * it_begin) * (unsigned)UB : PS_OOB;
+    ubase1[i] = (unsigned)blk * (unsigned)Ka1 * (unsigned)UB + (unsigned)(2 * it_begin - Ka0) * (unsigned)UB;
   }
   const unsigned lane16 = lane * 16;
   const unsigned lds0 = (unsigned)(size_t)smem_ps;
   auto issue = [&](int s) {                     // the DMA of local stage s into ring buffer s % NS (stages past the end: zeros)
     const unsigned buf = lds0 + (unsigned)(s % NS) * STAGE;
     const bool live = s < n16;
+    const bool src1 = 2 * it_begin + s >= Ka0;  // (wave-uniform: this stage's A slab lies in the second source)
+    const u32x4 rs_as = src1 ? rs_a1 : rs_a;
 #pragma unroll
     for (int i = 0; i < UHI; ++i) {
       const int u = wave + NW * i;
       if (u < U && !(dbg & 2)) {                 // (wave-uniform)
-        const unsigned off = (live && ubase[i] != PS_OOB) ? ubase[i] + (unsigned)s * (unsigned)UB : PS_OOB;
-        ps_dma<PL>(lane16 + off, u < FA ? rs_a : rs_b, buf + (unsigned)u * (unsigned)UB);
+        const unsigned off = (live && ubase[i] != PS_OOB) ? ((u < FA && src1) ? ubase1[i] : ubase[i]) + (unsigned)s * (unsigned)UB : PS_OOB;
+        ps_dma<PL>(lane16 + off, u < FA ? rs_as : rs_b, buf + (unsigned)u * (unsigned)UB);
       }
     }
   };
@@ -1098,6 +1112,12 @@ const char* igemm_ps_unsupported(const ldmk_igemm_args& a, int pcfg, int splitk)
   if (a.b_trans || a.upsample || a.skip_a0 || (a.splitk_counters && !(ps_probe_bits() & 8))) return "b_trans / upsample / fused skip / in-launch combine";
   if (a.a_tf != LDMK_TF_NONE && a.a_tf != LDMK_TF_LAYERNORM_FOLDED) return "no staging prologue: a_ps is what gets multiplied";
   if (a.K % 32 || a.N % 32) return "K and N must be multiples of 32";
+  if (a.a_ps1) {      // two A sources: columns [0, a_ps_k0) from a_ps, [a_ps_k0, K) from a_ps1 (igemm_ps_kernel only)
+    if (a.a_mode != LDMK_A_ROWS || pcfg == 6 || pcfg == 7) return "a_ps1: rows mode on tile_cfg 23..28 / 31..33 (not the conv-mode or warp-specialised tiles)";
+    if (a.batch > 1 || a.attn_kv_out || a.a_tf != LDMK_TF_NONE || a.epi == LDMK_EPI_GEGLU)
+      return "a_ps1: no batching, no fused QKV tiles, no folded LayerNorm, no GEGLU";
+    if (a.a_ps_k0 <= 0 || a.a_ps_k0 >= a.K || a.a_ps_k0 % 32) return "a_ps1: a_ps_k0 and K - a_ps_k0 must be positive multiples of 32";
+  }
   const long long kb = a.K / 16;
   if ((a.a_mode == LDMK_A_ROWS && (long long)((a.M + 31) / 32) * kb * pl * 1024 >= (1LL << 31)) || (long long)(a.N / 32) * kb * pl * 1024 >= (1LL << 31))
     return "an operand of 2 GiB or more";

@@ -42,6 +42,7 @@ class IgemmArgs(C.Structure):
         ("a_ps", _fp), ("a_ps_bstride", C.c_longlong), ("w_ps", _fp), ("w_ps_bstride", C.c_longlong), ("out_ps", _fp),
         ("w_scale_exp", C.c_int), ("range_flag", _fp),
         ("attn_kv_out", _fp), ("attn_tokens", C.c_int), ("attn_heads", C.c_int),
+        ("a_ps1", _fp), ("a_ps_k0", C.c_int),
     ]
 
 

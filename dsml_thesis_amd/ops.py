@@ -216,6 +216,30 @@ def pack_wps(w, batch=1, h2=False):
     return out
 
 
+def fold_pout(w2, b2, wpo, bpo, dtype=torch.float32):
+    """ff.net.2 followed by proj_out as ONE Linear on the K-concat [g | h2] (g: the GEGLU output, h2: ff.net.2's residual):
+        (h2 + g W2^T + b2) Wpo^T + bpo  =  [g | h2] W' + b',    W' = [W2^T Wpo^T ; Wpo^T],  b' = b2 Wpo^T + bpo.
+    w2 [C][4C], b2 [C], wpo [ch][C] (or the 1x1 convolution's [ch][C][1][1]), bpo [ch] in torch's layouts, any device -> (W' as
+    [5C][ch], the [K][N] form of pack_linear, and b' [ch]).  Composed in float64, rounded once to `dtype`."""
+    w2d, wpod = w2.double(), wpo.reshape(wpo.shape[0], wpo.shape[1]).double()
+    w = torch.cat([w2d.t() @ wpod.t(), wpod.t()], 0)
+    b = b2.double() @ wpod.t() + bpo.double()
+    return w.to(dtype).contiguous(), b.to(dtype).contiguous()
+
+
+# The F16X2 planes of W' share one exponent e (max |2^e W'| in [2^13, 2^14), h2_scale_exp).  The lo plane of an element of scaled
+# magnitude x is about 2^-11 x and stays a NORMAL fp16 (>= 2^-14) while x >= 2^-3, i.e. down to 2^-16 of the largest weight: a half
+# of W' whose largest element is above that keeps its full two-plane precision next to the other half.  (Below, lo falls into the
+# subnormals, quantum 2^-24 scaled = 2^-37 of the largest weight.)  W2^T Wpo^T is typically 10-100x smaller than Wpo^T: far inside.
+FOLD_POUT_H2_MIN_RATIO = 2.0 ** -16
+
+
+def fold_pout_h2_ok(w, k0):
+    """Whether both K-halves of W' ([0, k0) and [k0, K)) keep normal lo planes under the one F16X2 exponent of the matrix."""
+    top, bot = float(w[:k0].abs().max().item()), float(w[k0:].abs().max().item())
+    return min(top, bot) >= FOLD_POUT_H2_MIN_RATIO * max(top, bot) > 0.0
+
+
 def ln_stats_ps(x2d, eps=1e-5, out=None, ps=None, guard=0.0, flag=None, h2_flag=None):
     """LayerNorm (mean, rstd) per row AND the rows in the PS layout (one pass); returns (stats, ps).  h2_flag: the F16X2 planes."""
     rows, c = x2d.shape
@@ -281,7 +305,7 @@ def make_igemm_args(M, N, K, a0, c0, w, out, ldc, rows_per_sample, a1=None, c1=0
                     batch_vec=None, batch_vec_ld=0, residual=None, epi=L.EPI_NONE, batch=1, a_bstride=0, w_bstride=0,
                     out_bstride=0, alpha=1.0, splitk=0, splitk_ws=None, w_frag=None, tile_cfg=0, compute=0, ln_colsum=None,
                     splitk_counters=None, raw_slabs=False, a_split=None, w_bf16t=None, a_ps=None, w_ps=None, out_ps=None,
-                    range_flag=None, attn_kv=None):
+                    range_flag=None, attn_kv=None, a_ps1=None, a_ps_k0=0):
     a = L.IgemmArgs()
     # the struct holds raw device pointers: keep every operand alive as long as the args object lives (a temporary passed
     # inline -- bias=b.cuda() -- would otherwise be freed, and its block possibly re-used, before the launch is enqueued)
@@ -318,6 +342,9 @@ def make_igemm_args(M, N, K, a0, c0, w, out, ldc, rows_per_sample, a1=None, c1=0
         a.a_split, a.a_split_ld = _ptr(a_split), a_split.shape[-1]
     if a_ps is not None:          # pre-split tiles (tile_cfg 23..33): both operands in the PS layout
         a.a_ps, a.w_ps, a.out_ps = _ptr(a_ps), _ptr(w_ps), _ptr(out_ps)
+        if a_ps1 is not None:     # two A sources: columns [0, a_ps_k0) in a_ps, the rest in a_ps1
+            a.a_ps1, a.a_ps_k0 = _ptr(a_ps1), int(a_ps_k0)
+            a._keep = a._keep + (a_ps1,)
         if batch > 1:
             a.a_ps_bstride, a.w_ps_bstride = a_ps.shape[-1], w_ps.shape[-1]
         hit = _WPS_H2_EXP.get(w_ps.data_ptr())

@@ -31,6 +31,8 @@ SWITCHES = {
     "LDMK_PSC": ("1", "route", "0: no conv-mode pre-split tile for 3x3 convolutions; same bits"),
     "LDMK_PSC_FORCE": (None, "route", "'cfg,splitk': force the conv-mode pre-split tile for every eligible convolution (A/B runs)"),
     "LDMK_POUT_PS": ("0", "route", "1: SpatialTransformer.proj_out on a pre-split tile instead of the row GEMM (measured slower)"),
+    "LDMK_FOLD_POUT": ("1", "route", "0: the last block's ff.net.2 and proj_out stay two GEMMs instead of one pre-split GEMM on two A "
+                       "sources with the composed weight (other bits, same tolerance)"),
     "LDMK_ATTN_PS": ("1", "route", "0: attn1.to_out does not read the attention result in the PS layout"),
     "LDMK_ATTN_PRESPLIT": ("1", "route", "0: K / V are split inside the attention kernel instead of once by their producer; same bits"),
     "LDMK_ATTN_PRESPLIT_MIN_TOKENS": ("2048", "route", "tokens per sample from which K / V are pre-split"),

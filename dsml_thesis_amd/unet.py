@@ -144,6 +144,13 @@ def pack_spatial_transformer(P, sd, prefix, m):
         for k, nrm, b in (("qkv", "norm1", None), ("q2", "norm2", None), ("ff1", "norm3", P[q + "ff1b"])):
             P[q + k + "_ln"], P[q + k + "_ln#cs"], P[q + k + "_ln#b"] = ops.fold_layernorm(
                 P[q + k], sd[q + nrm + ".weight"], sd[q + nrm + ".bias"], b)
+    # the last block's ff.net.2 and proj_out composed into one Linear on [GEGLU output | ff.net.2's residual] (ops.fold_pout), for the
+    # two-source pre-split GEMM (emit_spatial_transformer): same eligibility as the `#p` copies of its two factors
+    if engine_ps_enabled():
+        q = f"{prefix}transformer_blocks.{m.depth - 1}."
+        if all(d % 32 == 0 for k in (q + "ff2", prefix + "pout") for d in P[k].shape):
+            P[prefix + "ffpo"], P[prefix + "ffpo#b"] = ops.fold_pout(sd[q + "ff.net.2.weight"], sd[q + "ff.net.2.bias"],
+                                                                     sd[prefix + "proj_out.weight"], sd[prefix + "proj_out.bias"])
 
 
 def attention_presplit(hw):
@@ -278,7 +285,7 @@ def pack_gemm_copies(P, unfolded=False):
     if engine_ps_enabled():
         for k in list(P):
             tail = k.rsplit(".", 1)[-1]
-            if tail in ("qkv_ln", "ff1_ln", "ff2", "o1", "pout") and P[k].dim() == 2 and P[k].shape[0] % 32 == 0 and P[k].shape[1] % 32 == 0:
+            if tail in ("qkv_ln", "ff1_ln", "ff2", "o1", "pout", "ffpo") and P[k].dim() == 2 and P[k].shape[0] % 32 == 0 and P[k].shape[1] % 32 == 0:
                 P[k + "#p"] = ops.pack_wps(P[k])
             elif tail in ("c1#wg", "c2#wg", "w#up") and P[k].shape[1] % 32 == 0 and P[k].shape[2] % 32 == 0:
                 P[k + "#p"] = ops.pack_wps(P[k], batch=P[k].shape[0])     # Winograd planes / upsampling phases (transforms write V in PS)
@@ -288,6 +295,8 @@ def pack_gemm_copies(P, unfolded=False):
                 tail = k.rsplit(".", 1)[-1]
                 if tail in ("qkv_ln", "ff1_ln", "ff2", "o1", "pout") and P[k].dim() == 2 and P[k].shape[0] % 32 == 0 and P[k].shape[1] % 32 == 0:
                     P[k + "#p2"] = ops.pack_wps(P[k], h2=True)
+                elif tail == "ffpo" and ops.fold_pout_h2_ok(P[k], P[k].shape[0] - P[k].shape[0] // 5):
+                    P[k + "#p2"] = ops.pack_wps(P[k], h2=True)       # (refused: one half's lo plane would go subnormal; no fold in F16X2)
                 elif tail in ("c1#wg", "c2#wg", "w#up") and P[k].shape[1] % 32 == 0 and P[k].shape[2] % 32 == 0:
                     P[k + "#p2"] = ops.pack_wps(P[k], batch=P[k].shape[0], h2=True)
                 elif tail in ("c1", "c2") and P[k].dim() == 2 and P[k].shape[0] % (9 * 32) == 0 and P[k].shape[1] % 32 == 0:
@@ -318,18 +327,19 @@ def emit_spatial_transformer(nb_, ctx_pg, P, sd, prefix, m, x, h, w, L_ctx, ctx_
 
     # The arithmetic is a property of the SITE (engine.ArithSites): `attn1` = LN1 -> fused QKV -> self attention -> to_out (they hand
     # each other split operands: the QKV epilogue writes the attention's K / V tiles, the attention writes to_out's A operand), `ff` =
-    # LN3 -> GEGLU projection -> ff.net.2 [-> proj_out on a pre-split tile], `attn2` (contexts of several tokens), `proj_in`,
+    # LN3 -> GEGLU projection -> ff.net.2 [-> proj_out on a pre-split tile, or folded into ff.net.2], `attn2` (contexts of several tokens), `proj_in`,
     # `proj_out`.  Inside `with nb_.site(...)` nb_.h2_flag is that site's range flag, or None when the site runs in bf16x3.
     hf = lambda: nb_.h2_flag
     psfx = lambda: "#p2" if hf() is not None else "#p"       # the PS weight copies in the form of the site's arithmetic
 
     kv_state = {"tiles": None}
 
-    def ln_lin(x2d, wkey, geglu, out_ps=None, attn_kv=None):
+    def ln_lin(x2d, wkey, geglu, out_ps=None, attn_kv=None, keep_xs=False):
         """LayerNorm statistics + the Linear the LayerNorm is folded through.  With a pre-split plan for the GEMM
         (engine.ps_query: csrc/igemm_ps.hip) the statistics pass also writes the rows in the PS layout and the GEMM moves them
         to LDS by LDS-DMA -- every element is split once, by this pass, instead of once per N-tile inside the GEMM.
-        `out_ps`: (GEGLU only) the result goes out in the PS layout ONLY, for ff.net.2."""
+        `out_ps`: (GEGLU only) the result goes out in the PS layout ONLY, for ff.net.2.  `keep_xs` (with out_ps): the PS copy of the
+        raw rows is not released but returned, for a second consumer."""
         wp = P[wkey]
         N_ = wp.shape[1]
         h2_flag = hf()
@@ -347,6 +357,8 @@ def emit_spatial_transformer(nb_, ctx_pg, P, sd, prefix, m, x, h, w, L_ctx, ctx_
                 kv_state["tiles"] = attn_kv[0]
             y = nb_.lin_ps(plan, rows, C_, xs, wp, P[wkey + psfx()], P[wkey + "#b"], hw, geglu=geglu, out_ps=out_ps,
                            tf=L.TF_LAYERNORM_FOLDED, row_stats=stats, ln_colsum=P[wkey + "#cs"], **kw)
+            if keep_xs:
+                return xs
             nb_.release(xs)
             return y
         assert out_ps is None
@@ -437,7 +449,8 @@ def emit_spatial_transformer(nb_, ctx_pg, P, sd, prefix, m, x, h, w, L_ctx, ctx_
     def ff_section(q, h2, last):
         """GEGLU feed-forward: LN3 folded into the first GEMM, gate in its epilogue, ff.net.2 + residual.  When both GEMMs run on
         pre-split tiles (engine.ps_query) the intermediate exists in the PS layout only -- written by the GEGLU epilogue, split
-        once -- never as an fp32 tensor.  Returns (hcur, hc_ps, plan_p)."""
+        once -- never as an fp32 tensor.  Returns (hcur, hc_ps, plan_p, out): `out` is the transformer's output when the last block's
+        ff.net.2 took proj_out with it (then hcur is None: that tensor is never made)."""
         Nf = P[q + "ff2"].shape[0]
         plan_g = plan_f = None
         if not unfolded and q + "ff1_ln" + psfx() in P and q + "ff2" + psfx() in P:
@@ -445,6 +458,17 @@ def emit_spatial_transformer(nb_, ctx_pg, P, sd, prefix, m, x, h, w, L_ctx, ctx_
             plan_f = nb_.ps_query(rows, C_, Nf)
         if plan_g is not None and plan_f is not None:
             f_ps = pg.alloc_ps(rows, Nf)
+            # The last block's ff.net.2 and proj_out as ONE pre-split GEMM on two A sources (csrc/igemm_ps.hip, args.a_ps1): both maps
+            # are linear, so out = x_in + [g | h2] W' + b' with W', b' composed at pack time (ops.fold_pout).  g is f_ps; the raw h2
+            # rows are the PS tensor the LN3 statistics pass wrote for the GEGLU GEMM, kept alive for this launch.  hcur is not made.
+            plan_fp = (nb_.ps_query(rows, m.ch, Nf + C_) if (last and prefix + "ffpo" + psfx() in P
+                                                            and switches.get("LDMK_FOLD_POUT", "1") != "0") else None)
+            if plan_fp is not None:
+                xs = ln_lin(h2, q + "ff1_ln", True, out_ps=f_ps, keep_xs=True)
+                out = nb_.lin_ps(plan_fp, rows, Nf + C_, f_ps, P[prefix + "ffpo"], P[prefix + "ffpo" + psfx()], P[prefix + "ffpo#b"], hw,
+                                 residual=xr, stats=True, a_ps1=xs, a_ps_k0=Nf)
+                nb_.release(f_ps, xs, h2)
+                return None, None, None, out
             ln_lin(h2, q + "ff1_ln", True, out_ps=f_ps)
             # the last block's ff.net.2 also writes its result pre-split when proj_out runs on a pre-split tile
             # (proj_out on a pre-split tile: built and tested, off by default -- its epilogue carries the GroupNorm records of the block
@@ -456,7 +480,7 @@ def emit_spatial_transformer(nb_, ctx_pg, P, sd, prefix, m, x, h, w, L_ctx, ctx_
             hcur = nb_.lin_ps(plan_f, rows, Nf, f_ps, P[q + "ff2"], P[q + "ff2" + psfx()], sd[q + "ff.net.2.bias"], hw, out=h2, residual=h2,
                               out_ps=hc_ps)
             nb_.release(f_ps)
-            return hcur, hc_ps, plan_p
+            return hcur, hc_ps, plan_p, None
         if unfolded:
             pg.add("ldmk_ln_stats", p_(h2), rows, C_, 1e-5, p_(stats))
             f = lin(h2, P[q + "ff1"], P[q + "ff1b"], hw, geglu=True, tf=L.TF_LAYERNORM, row_stats=stats,
@@ -465,7 +489,7 @@ def emit_spatial_transformer(nb_, ctx_pg, P, sd, prefix, m, x, h, w, L_ctx, ctx_
             f = ln_lin(h2, q + "ff1_ln", True)
         hcur = lin(f, P[q + "ff2"], sd[q + "ff.net.2.bias"], hw, residual=h2, out=h2, wf=P.get(q + "ff2#f"))
         nb_.release(f)
-        return hcur, None, None
+        return hcur, None, None, None
 
     for d in range(m.depth):
         q = f"{prefix}transformer_blocks.{d}."
@@ -478,7 +502,10 @@ def emit_spatial_transformer(nb_, ctx_pg, P, sd, prefix, m, x, h, w, L_ctx, ctx_
                 h2 = attn2_section(q, h1, att)
         ff_site = q + "ff"
         with nb_.site(ff_site):
-            hcur, hc_ps, plan_p = ff_section(q, h2, d == m.depth - 1)
+            hcur, hc_ps, plan_p, out = ff_section(q, h2, d == m.depth - 1)
+    if out is not None:
+        nb_.release(stats)
+        return out.view(n, h, w, m.ch)
     if hc_ps is not None:
         with nb_.site(ff_site):       # (proj_out reads the operand ff.net.2 wrote pre-split: same site, same arithmetic)
             out = nb_.lin_ps(plan_p, rows, C_, hc_ps, P[prefix + "pout"], P[prefix + "pout" + psfx()], sd[prefix + "proj_out.bias"], hw, residual=xr,

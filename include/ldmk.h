@@ -185,6 +185,11 @@ typedef struct ldmk_igemm_args {
   int attn_tokens;           /*   stored in `out` but written as the attention's pre-split K / V tiles                               */
   int attn_heads;            /*   (ldmk_attn_kv_split_h2_bytes(M / attn_tokens, attn_tokens, attn_heads) bytes; attn_tokens % 64 == 0, */
                              /*   dividing M): bit for bit what ldmk_attn_self_h2's pre-pass writes from the fp32 K / V               */
+  /* ---- two A sources on the rows-mode pre-split tiles (tile_cfg 23..28 / 31..33): A = [A0 | A1] without a tensor that holds it     */
+  const void* a_ps1;         /* optional: columns [a_ps_k0, K) of A, a PS tensor [M][K - a_ps_k0] of its own; a_ps is then the PS      */
+  int a_ps_k0;               /*   tensor [M][a_ps_k0] of columns [0, a_ps_k0).  Both widths positive multiples of 32; no batching,     */
+                             /*   a_tf NONE, no GEGLU, no attn_kv_out.  Bitwise the single-source result on pack([A0 | A1]) at equal   */
+                             /*   (tile_cfg, splitk): same products, same order, same split-K partition (32-deep chunks of all of K)   */
 } ldmk_igemm_args;
 
 /* size in bytes of the PS layout of a [rows][k] matrix (-1: k not a multiple of 16) */
