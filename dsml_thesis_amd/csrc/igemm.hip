@@ -84,7 +84,11 @@ __device__ __forceinline__ void ig_lean_epilogue(const ldmk_igemm_args& p, f32x1
         outp[obase + (unsigned)(((r & 3) + 8 * (r >> 2)) * p.ldc)] = vals[r];
       }
       if (p.stats_out) {
-        const float shift = __shfl(vals[0], l31, 64);      // row 0 of the tile
+        float tsum = 0.f;                                  // shift = the tile's own mean: see gn_tile_record
+#pragma unroll
+        for (int r = 0; r < 16; ++r) tsum += vals[r];
+        tsum += __shfl_xor(tsum, 32, 64);
+        const float shift = tsum * (1.0f / 32.0f);
         float sm = 0.f, sq = 0.f;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -931,7 +935,11 @@ __global__ __launch_bounds__(256) void igemm_kernel(const ldmk_igemm_args p, con
       if (p.stats_out && rowbase + i * 32 < p.M) {
         // GroupNorm partial record of this 32-row tile x column (same record as gn_partial_kernel):
         // the 32 rows of the tile sit in 16 registers x 2 half-waves of the lane pair (l31, l31+32)
-        const float shift = __shfl(vals[0], l31, 64);      // row 0 of the tile
+        float tsum = 0.f;                                  // shift = the tile's own mean: see gn_tile_record
+#pragma unroll
+        for (int r = 0; r < 16; ++r) tsum += vals[r];
+        tsum += __shfl_xor(tsum, 32, 64);
+        const float shift = tsum * (1.0f / 32.0f);
         float sm = 0.f, sq = 0.f;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -1032,7 +1040,10 @@ __global__ __launch_bounds__(256) void igemm_reduce_stats_kernel(const ldmk_igem
   __syncthreads();
   if (threadIdx.x < 64 && c0 + threadIdx.x < p.N) {
     const int c = threadIdx.x;
-    const float shift = tile[0][c];
+    float tsum = 0.f;                                      // shift = the tile's own mean: see gn_tile_record
+#pragma unroll
+    for (int r = 0; r < 32; ++r) tsum += tile[r][c];
+    const float shift = tsum * (1.0f / 32.0f);
     float sm = 0.f, sq = 0.f;
 #pragma unroll
     for (int r = 0; r < 32; ++r) {

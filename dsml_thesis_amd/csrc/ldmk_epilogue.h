@@ -47,10 +47,16 @@ __device__ __forceinline__ float col_finish(float acc_alpha, float bias, float v
 
 // GroupNorm partial record of one 32-row tile x column (same record as gn_partial_kernel): the 32 rows of the tile sit in
 // 16 registers x 2 half-waves of the lane pair (l31, l31 + 32); three floats per tile and column: shift, sum (x - shift),
-// sum (x - shift)^2.  The caller guards (stats_out set, tile inside M).
+// sum (x - shift)^2, shift = the fp32 mean of the tile's 32 values.  The caller guards (stats_out set, tile inside M).
 __device__ __forceinline__ void gn_tile_record(const float (&vals)[16], float* stats_out, const int tile_row, const int N,
                                                const int col, const int l31, const int half) {
-  const float shift = __shfl(vals[0], l31, 64);      // row 0 of the tile
+  // shift = the tile's own mean (any fp32 value serves: the finalize un-shifts in double with the stored one).  With row 0 as the
+  // shift an outlier first row left partial sums of ~70 sigma-units and 2-6 x 2^-24 of error in the group mean.
+  float tsum = 0.f;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) tsum += vals[r];
+  tsum += __shfl_xor(tsum, 32, 64);                   // (a + b == b + a: both halves hold the same bits)
+  const float shift = tsum * (1.0f / 32.0f);
   float sm = 0.f, sq = 0.f;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {

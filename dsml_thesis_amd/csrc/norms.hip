@@ -7,7 +7,9 @@ namespace ldmk {
 
 constexpr int GN_PIX = 32;   // pixels per partial-sum chunk == the MFMA row-tile, so igemm epilogues can emit partials
 
-// pass 1 (stand-alone form; igemm / its split-K reduce emit the same records from their epilogue):
+// pass 1 (stand-alone form; the GEMM epilogues and the split-K reduce emit records of the same format, with the chunk's fp32 mean as
+// the shift -- they hold the 32 values in registers / LDS; this pass streams its rows and takes the first value, which leaves more
+// fp32 error in sum(x - shift) when that value is an outlier: see DESIGN section 4):
 // per-(sample, chunk, channel) shifted sum and sum of squares.  Thread <-> channel, so a wave reads
 // 64 consecutive floats of one NHWC pixel row: fully coalesced.
 __global__ __launch_bounds__(256) void gn_partial_kernel(const float* __restrict__ x, int C, int hw, int chunks,

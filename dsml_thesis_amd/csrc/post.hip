@@ -463,7 +463,8 @@ extern "C" int ldmk_post(const ldmk_post_args* args, void* stream) {
                      "floats (ldmk_post_scratch_elems), %lld given", p.rows_per_sample, need, p.gn_scratch ? p.gn_scratch_elems : 0LL);
     const bool plain_src = p.nslab == 1 && !p.bias && !p.batch_vec && !p.residual && p.alpha == 1.0f;
     LDMK_REQUIRE(p.raw_out || plain_src, "ldmk_post: a pending source needs raw_out (the apply launch reads the finished values)");
-    if (plain_src) p.raw_out = nullptr;                       // nothing to store: the apply launch reads src itself
+    // raw_out is written whenever it is given (a plain source too: the caller asked for the copy); the stats launch stores it
+    // and the apply launch reads it back.  Without raw_out the source is plain and the apply launch reads src itself.
     hipLaunchKernelGGL(post_gnstat_kernel, dim3(chunks, ns), dim3(256), (size_t)GS_R * C * sizeof(float), st, p, p.gn_scratch);
     hipLaunchKernelGGL(post_gnapply_kernel, dim3(chunks, ns), dim3(256), 0, st, p, p.gn_scratch, chunks);
     return check_launch("ldmk_post(groupnorm, row-tiled)");
