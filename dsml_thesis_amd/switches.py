@@ -74,6 +74,8 @@ SWITCHES = {
     "LDMK_IG_LEAN": ("1", "library", "0: the general igemm epilogue everywhere instead of the operand-set specialised copies; same bits"),
     "LDMK_PS_NFAST": ("1", "library", "as LDMK_IG_NFAST, pre-split tiles"),
     "LDMK_PS_LEAN": ("1", "library", "as LDMK_IG_LEAN, pre-split tiles"),
+    "LDMK_WINO_STAGED": ("1", "library", "0: the Winograd input / output transforms on their first kernels (a thread loads its own 4x4 "
+                         "window / walks a band's tiles) instead of the LDS-staged / vectorised ones; same bits"),
     "LDMK_WGRAD_TR": ("1", "library", "0: bf16 weight-gradient GEMM with the strided gather instead of transposed LDS reads (A/B)"),
     # ---- bench.py
     "LDMK_BENCH_BACKEND": ("nccl", "bench", "'gloo': rehearse the N > 1 path of bench.py on a one-GPU box"),

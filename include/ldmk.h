@@ -285,6 +285,19 @@ int ldmk_winograd_input_ps_h2(const float* x0, int c0, const float* x1, int c1, 
                               void* v_ps, int* range_flag, void* stream);
 int ldmk_winograd_output(const float* m, const float* bias, const float* batch_vec, int batch_vec_ld, const float* residual,
                          float* out, float* stats_out, int n, int h, int w, int cout, void* stream);
+/* The three entry points above launch the LDS-staged input transform (each pixel read and activated once per workgroup) and
+ * the vectorised output transform (thread <-> tile x 4 channels) where the shape allows, the first kernels (thread <-> its own
+ * 4x4 window / thread <-> channel) elsewhere and everywhere under LDMK_WINO_STAGED=0; same bits either way.  The _route
+ * functions say which, from the shape alone (1: staged / vectorised, 0: first kernel); the _v1 entry points always launch the
+ * first kernels (the reference of the tests, the A/B baseline). */
+int ldmk_winograd_input_ps_route(int n, int h, int w, int c0, int c1);
+int ldmk_winograd_output_route(int n, int h, int w, int cout, int with_stats);
+int ldmk_winograd_input_ps_v1(const float* x0, int c0, const float* x1, int c1, const float* coef, int silu, int n, int h, int w,
+                              void* v_ps, void* stream);
+int ldmk_winograd_input_ps_h2_v1(const float* x0, int c0, const float* x1, int c1, const float* coef, int silu, int n, int h, int w,
+                                 void* v_ps, int* range_flag, void* stream);
+int ldmk_winograd_output_v1(const float* m, const float* bias, const float* batch_vec, int batch_vec_ld, const float* residual,
+                            float* out, float* stats_out, int n, int h, int w, int cout, void* stream);
 
 /* Nearest-x2 upsampling + Conv2d 3x3 (openaimodel.py:107-118) as four 2x2-tap convolutions on the low-resolution input
  * (one per output parity; exact: the collapsed taps carry the summed weights) -- 4/9 of the multiplications:

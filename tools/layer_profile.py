@@ -31,6 +31,8 @@ def dump(latent, batch, path, graph=False):
             from dsml_thesis_amd.engine import plan_key
             calls.append(dict(name=name, M=a.M, N=a.N, K=a.K, conv=a.a_mode, tf=a.a_tf, epi=a.epi, cfg=a.tile_cfg,
                               sk=a.splitk, key=plan_key(a, a.M), batch=max(1, a.batch), raw=int(a.raw_slabs), compute=int(a.compute)))
+        elif name in MOVES:
+            calls.append(dict(name=name, move=MOVES[name](*[getattr(v, "value", v) or 0 for v in args])))
         else:
             calls.append(dict(name=name))
     side = [c[3] for c in getattr(run.pg, "side_calls", None) or []]       # launches on the forked stream (parallel branch)
@@ -45,6 +47,22 @@ def dump(latent, batch, path, graph=False):
         run.step()
     torch.cuda.synchronize()
 
+
+def _wino_in(pl):
+    # (x0, c0, x1, c1, coef, silu, n, h, w, V, ...): x read once, 16 planes of pl x 2 bytes per element written
+    return lambda x0, c0, x1, c1, coef, silu, n, h, w, *rest: dict(shape=f"{c0}+{c1} @{h}x{w} n={n}",
+                                                                   bytes=n * h * w * (c0 + c1) * 4 + 16 * n * (h // 2) * (w // 2) * (c0 + c1) * 2 * pl)
+
+
+# the pure data-movement passes whose effective rate the join prints: entry point -> (shape label, bytes the pass has to move)
+MOVES = {
+    "ldmk_winograd_input_ps": _wino_in(3), "ldmk_winograd_input_ps_h2": _wino_in(2),
+    # (m, bias, bvec, ld, res, out, stats, n, h, w, cout): 16 planes of M read, out written, the residual read where there is one
+    "ldmk_winograd_output": lambda m, bias, bvec, ld, res, out, stats, n, h, w, cout: dict(
+        shape=f"->{cout} @{h}x{w} n={n}" + (" +res" if res else ""), bytes=n * h * w * cout * 4 * (4 + 1 + (1 if res else 0))),
+    # (x0, c0, x1, c1, coef, y, n, hw, silu, flag): x read, two fp16 planes written
+    "ldmk_gn_apply_ps_h2": lambda x0, c0, x1, c1, coef, y, n, hw, silu, flag: dict(shape=f"{c0}+{c1} {hw} px n={n}", bytes=n * hw * (c0 + c1) * 8),
+}
 
 KERNEL_OF = {"ldmk_igemm": ("igemm_kernel", "igemm_ws_kernel", "igemm_ps_kernel", "igemm_psc_kernel", "igemm_pw_kernel", "rgemm_kernel", "sgemm_kernel"), "ldmk_post": ("post_",),
              "ldmk_gn_apply_ps_h2": ("gn_apply_ps_h2",),
@@ -66,7 +84,9 @@ def join(d):
     calls = prog["calls"]
     tr = glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True)[0]
     rows = [r for r in csv.DictReader(open(tr)) if "ldmk::" in r["Kernel_Name"]]
-    rows.sort(key=lambda r: int(r["Start_Timestamp"]))
+    # dispatch order, not start order: one queue, and the start stamps of two back-to-back dispatches can come out swapped by a
+    # few microseconds (a short kernel behind a long one), which is no reordering of the program
+    rows.sort(key=lambda r: int(r["Dispatch_Id"]))
     per = sum(2 if (c["name"] in ("ldmk_post", "ldmk_attn_self_x3p", "ldmk_attn_self_x3p_ps", "ldmk_attn_self_h2", "ldmk_attn_self_h2_ps") or (c["name"] == "ldmk_igemm" and c.get("sk", 1) > 1 and not 7 <= c.get("cfg", 0) <= 12)) else 1
               for c in calls) + 1
     # the last step of the trace: find it by walking back from the end to the step's first kernel (timestep_embedding)
@@ -147,6 +167,20 @@ def join(d):
         fam_t += d_ if fl else 0.0
         fam_f += fl
         print(f"{key:75s} {n:3d} {d_:10.1f} {100 * d_ / tot:6.2f} {tfs:8.1f}  main {mn / n:6.1f} us/call" if fl else f"{key:75s} {n:3d} {d_:10.1f} {100 * d_ / tot:6.2f}")
+    moves = {}
+    for c, d_ in out:
+        if "move" in c:
+            m = moves.setdefault((c["name"], c["move"]["shape"]), [0, 0.0, 0])
+            m[0] += 1
+            m[1] += d_
+            m[2] += c["move"]["bytes"]
+    if moves:
+        print("data-movement passes, per shape: launches, us per launch, bytes the pass has to move (by shape), effective rate")
+        for (name, shape), (n, d_, by) in sorted(moves.items()):
+            print(f"  {name:28s} {shape:28s} {n:3d} {d_ / n:8.1f} us {by / n / 1e6:8.1f} MB {by / d_ * 1e-6:6.2f} TB/s")
+        for name in sorted({k[0] for k in moves}):
+            n, d_, by = (sum(v[i] for k, v in moves.items() if k[0] == name) for i in range(3))
+            print(f"  {name:28s} {'all':28s} {n:3d} {d_:8.1f} us total {by / 1e9:6.2f} GB {by / d_ * 1e-6:6.2f} TB/s")
     print(f"GEMM family (LDS-tiled igemm + row GEMM): {fam_f * 1e-9:.1f} GFLOP (fp32-equivalent 2MNK) in {fam_t / 1e3:.3f} ms = "
           f"{fam_f / (fam_t * 1e-6) / 1e12:.1f} TFLOP/s = {fam_f / (fam_t * 1e-6) / 1e12 / PEAK_F32_MFMA:.3f} of the f32 matrix peak "
           f"(rows marked bf16x3 / f16x2 execute 6 / 3 16-bit MFMA FLOPs per counted FLOP: their ceilings are {PEAK_BF16_MFMA / 6:.1f} / {PEAK_BF16_MFMA / 3:.1f})")
