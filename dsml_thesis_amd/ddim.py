@@ -183,18 +183,35 @@ class DDIMSampler(object):
             ctx_in, cat_in = ctx, cat
         ncat = 0 if cat_in is None else cat_in.shape[1]
         L_ctx = 0 if ctx_in is None else ctx_in.shape[1]          # 0: unconditional UNet (no cross-attention)
-        unet.policy_batch = None if policy_batch is None else (2 * policy_batch if cfg else policy_batch)
-        pg = unet.program(nb, shape[2], shape[3], L_ctx, ncat)
+        policy_nb = None if policy_batch is None else (2 * policy_batch if cfg else policy_batch)
+        y_emb = None if y_in is None else unet.label_emb.weight.detach().float()[y_in.to(dev, torch.int64)]
+        if hasattr(self.model, "split_input_params"):
+            # patch-wise (ddpm.py:904-986): the latent lives in a full-size buffer of nb items ([uncond | cond] under guidance, so
+            # ldmk_ddim_step's contract holds); one step = unfold -> the program at batch L*nb -> fold -> the update on the
+            # full-size tensors.  Context / concat crops are written once per run.
+            pe = self.model._patched_eval(nb, shape[1], shape[2], shape[3], L_ctx, ncat, policy_batch=policy_nb)
+            pg = pe.pg
+            pe.set_cond(ctx_in, cat_in, y_emb)
+            x_buf, eps, run_net = pe.x, pe.eps, pe.run
+            loops = pe.loops.setdefault("ddim", {})        # (never the plain loop's state of the same program)
+        else:
+            unet.policy_batch = policy_nb
+            pg = unet.program(nb, shape[2], shape[3], L_ctx, ncat)
+            x_buf, eps, run_net = pg.inputs["x"], pg.outputs["eps"], pg.run
+            if L_ctx:
+                pg.inputs["context"].copy_(ctx_in.reshape(nb * L_ctx, -1))
+            if ncat:
+                pg.inputs["c_concat"].copy_(cat_in)
+            if y_emb is not None:
+                pg.inputs["y_emb"].copy_(y_emb)
+            pg.ctx_program.run()                           # context-only projections: once per sample() call
+            # loop state (buffers, the captured step) lives ON the launch program it was captured over and dies with it: when the
+            # model drops its programs (a re-pack, an arithmetic fall-back) nothing keeps the old workspace or its hipGraph alive,
+            # and a new program can never be handed buffers of another batch size (rounds 2-4 keyed a sampler-side cache by id(pg))
+            loops = pg.__dict__.setdefault("_ddim_loops", {})
         lib = pg.lib
-        x_buf = pg.inputs["x"]
-        if L_ctx:
-            pg.inputs["context"].copy_(ctx_in.reshape(nb * L_ctx, -1))
-        if ncat:
-            pg.inputs["c_concat"].copy_(cat_in)
-        if y_in is not None:
-            pg.inputs["y_emb"].copy_(unet.label_emb.weight.detach().float()[y_in.to(dev, torch.int64)])
-        pg.ctx_program.run()                               # context-only projections: once per sample() call
-        img = x_buf[:b]                                    # the latent lives in the UNet's input buffer
+        n_ts = pg.inputs["t"].numel()                      # (patch-wise: L*nb entries, all the current timestep)
+        img = x_buf[:b]                                    # the latent lives in the UNet's input buffer (patch-wise: the full-size one)
         img.copy_(img0)
         if cfg:
             x_buf[b:].copy_(img0)
@@ -221,10 +238,6 @@ class DDIMSampler(object):
             assert not invert and timesteps is None
             n_run = int(n_steps)
         assert 0 < n_run <= S, (n_run, S)
-        # loop state (buffers, the captured step) lives ON the launch program it was captured over and dies with it: when the model
-        # drops its programs (a re-pack, an arithmetic fall-back) nothing keeps the old workspace or its hipGraph alive, and a
-        # new program can never be handed buffers of another batch size (rounds 2-4 keyed a sampler-side cache by id(pg))
-        loops = pg.__dict__.setdefault("_ddim_loops", {})
         lkey = (cfg, float(unconditional_guidance_scale), self._sched_key, need_noise, bool(use_graph), noise is None, bool(invert),
                 bool(ddim_use_original_steps), n_run)
         st = None if extras else loops.get(lkey)           # (option runs capture their own tensors: never cached)
@@ -234,7 +247,6 @@ class DDIMSampler(object):
             if not extras:
                 loops[lkey] = st
         pred_x0, step_idx, nz_buf = st["pred_x0"], st["step_idx"], st["nz"]
-        eps = pg.outputs["eps"]
         per = img0[0].numel()
         scale = float(unconditional_guidance_scale)
         first = 0 if invert else n_run - 1
@@ -264,7 +276,7 @@ class DDIMSampler(object):
                 if noise_dropout > 0.:
                     nz_buf.copy_(torch.nn.functional.dropout(nz_buf, p=noise_dropout))
             a_prev = table[step_idx.long(), 1] if quantize_denoised else None      # read before the kernel advances the counter
-            pg.run()
+            run_net()
             e_ptr, k_cfg = eps.data_ptr(), (1 if cfg else 0)
             if score_corrector is not None:                # ddim.py:179-181 acts on the guidance-combined score
                 e_t = eps[:b] if not cfg else eps[:b] + scale * (eps[b:] - eps[:b])
@@ -273,7 +285,7 @@ class DDIMSampler(object):
                 e_ptr, k_cfg = eps_c.data_ptr(), 0
             rc = lib.ldmk_ddim_step(img.data_ptr(), e_ptr, 0 if nz_buf is None else nz_buf.data_ptr(),
                                     table.data_ptr(), step_idx.data_ptr(), scale, k_cfg, img.data_ptr(),
-                                    pred_x0.data_ptr(), per, b, ts_table.data_ptr(), pg.inputs["t"].data_ptr(), nb, adv, S,
+                                    pred_x0.data_ptr(), per, b, ts_table.data_ptr(), pg.inputs["t"].data_ptr(), n_ts, adv, S,
                                     torch.cuda.current_stream().cuda_stream)
             L.check(rc, "ldmk_ddim_step")
             if quantize_denoised:                          # x_prev = sqrt(a_prev) Q(pred_x0) + dir_xt + noise (ddim.py:194-202)

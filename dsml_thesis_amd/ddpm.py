@@ -252,7 +252,84 @@ class LatentDiffusion(_Base):
                 kwargs.update(cond_concat)
             else:
                 kwargs["c_concat"] = cond_concat if isinstance(cond_concat, list) else [cond_concat]
+        if hasattr(self, "split_input_params"):
+            if return_ids:
+                raise NotImplementedError("apply_model: return_ids with split_input_params (the reference asserts, ddpm.py:906)")
+            return self._apply_model_patched(x_noisy, t, kwargs)
         return self.model(x_noisy, t, **kwargs)
+
+    # ---- patch-wise evaluation (split_input_params, ddpm.py:904-986): crops as batch items, see patches.py -------------
+    def _patch_cond_check(self, has_ctx, has_cat):
+        """What the reference's patch-wise apply_model can be given (ddpm.py:905-974): ONE conditioning entry; an image-like
+        `cond_stage_key` means that entry is cropped along with x, which is built for the channel concat."""
+        from .patches import IMAGE_COND_KEYS
+        if has_ctx and has_cat:
+            raise NotImplementedError("split_input_params: more than one conditioning entry (hybrid / c_crossattn + c_concat): "
+                                      "the reference asserts len(cond) == 1 (ddpm.py:905)")
+        if self.cond_stage_key == "coordinates_bbox":
+            raise NotImplementedError("split_input_params: cond_stage_key 'coordinates_bbox' (per-patch bounding-box tokens, "
+                                      "ddpm.py:931-971) is not built")
+        image_like = self.cond_stage_key in IMAGE_COND_KEYS and bool(self.model.conditioning_key)
+        if has_ctx and image_like:
+            raise NotImplementedError(f"split_input_params: cond_stage_key {self.cond_stage_key!r} makes the reference crop the "
+                                      "conditioning tensor (ddpm.py:919-929); that is built for a channel-concat conditioning only")
+        if has_cat and not image_like:
+            raise ValueError(f"split_input_params: a channel-concat conditioning with cond_stage_key {self.cond_stage_key!r}: the "
+                             "reference hands every crop the full-size tensor (ddpm.py:973-974) and fails on the shapes")
+
+    def _patched_eval(self, nb, chans, h, w, L_ctx=0, ncat=0, policy_batch="keep"):
+        """The PatchedEval for `nb` full-size (chans,h,w) items under the current split_input_params.  It lives on the launch
+        program it drives, so a re-pack of the weights drops it together with that program.  `policy_batch` (the samplers'
+        sharding-invariant tile choice) counts full-size items; the program's batch is that times the number of crops."""
+        from . import patches
+        self._patch_cond_check(bool(L_ctx), bool(ncat))
+        params = self.split_input_params
+        unet = self.model.diffusion_model
+        dev = next(unet.parameters()).device
+        g = patches.geometry((h, w), params["ks"], params["stride"], params=params, device=dev)
+        n_crops = g.ly * g.lx
+        if policy_batch != "keep":
+            unet.policy_batch = None if policy_batch is None else n_crops * policy_batch
+        pg = unet.program(n_crops * nb, g.ks[0], g.ks[1], L_ctx, ncat)
+        key = (nb, chans, h, w, g.ks, g.stride) + patches.params_key(params)
+        cache = pg.__dict__.setdefault("_patched", {})
+        if key not in cache:
+            cache[key] = patches.PatchedEval(pg, g, nb, chans)
+        return cache[key]
+
+    def _apply_model_patched(self, x_noisy, t, kwargs):
+        from .unet import MAX_ARITHMETIC_PASSES
+        unet = self.model.diffusion_model
+        if not x_noisy.is_cuda:
+            raise L.LdmkError("apply_model: input must be a CUDA tensor (no CPU fallback)")
+        ctx, cat = kwargs.get("c_crossattn"), kwargs.get("c_concat")
+        adm = self.model.conditioning_key == "adm"
+        if self.model.conditioning_key is None:
+            ctx = cat = None
+        if isinstance(ctx, (list, tuple)):
+            ctx = None if ctx[0] is None else (ctx[0] if adm else torch.cat(list(ctx), 1))
+        if isinstance(cat, (list, tuple)):
+            cat = None if cat[0] is None else torch.cat(list(cat), 1)
+        nb, chans, h, w = x_noisy.shape
+        y_emb = None
+        if adm:
+            assert ctx is not None and ctx.dim() == 1 and cat is None, "conditioning_key 'adm': cond = class labels (B,)"
+            y_emb, ctx = unet.label_emb.weight.detach().float()[ctx.to(x_noisy.device, torch.int64)], None
+        L_ctx = 0 if ctx is None else ctx.shape[1]
+        ncat = 0 if cat is None else cat.shape[1]
+        for _ in range(MAX_ARITHMETIC_PASSES):
+            pe = self._patched_eval(nb, chans, h, w, L_ctx, ncat)
+            pe.x.copy_(x_noisy)
+            pe.set_t(t)
+            pe.set_cond(ctx, cat, y_emb)
+            pe.run()
+            if torch.cuda.is_current_stream_capturing():
+                break
+            first = not getattr(pe.pg, "ln_checked", False)         # (as UNetModel.forward: the data-dependent range flags)
+            pe.pg.ln_checked = True
+            if not unet.flags_tripped(check_layernorm=first):
+                break
+        return pe.eps.clone()
 
     def q_sample(self, x_start, t, noise=None):
         """ddpm.py:230-233."""
@@ -274,14 +351,22 @@ class LatentDiffusion(_Base):
         """ddpm.py:706-764 -> VQModelInterface.decode."""
         if predict_cids:
             raise NotImplementedError("decode_first_stage(predict_cids=True) is unused on the sampling path")
-        if hasattr(self, "split_input_params"):
-            raise NotImplementedError("patch-wise (split_input_params) decoding is unused by the shipped configs")
         z = 1. / self.scale_factor * z
+        split = getattr(self, "split_input_params", None)
+        if split is not None and split["patch_distributed_vq"]:           # ddpm.py:716-753: every crop is quantised on its own
+            from .patches import first_stage_patched
+            return first_stage_patched(lambda c: self.first_stage_model.decode(c, force_not_quantize=force_not_quantize), z, split,
+                                       uf=split["vqf"])
         return self.first_stage_model.decode(z, force_not_quantize=force_not_quantize)
 
     @torch.no_grad()
     def encode_first_stage(self, x):
         """ddpm.py:826-864 -> VQModelInterface.encode (no quantisation)."""
+        split = getattr(self, "split_input_params", None)
+        if split is not None and split["patch_distributed_vq"]:           # ddpm.py:828-859
+            from .patches import first_stage_patched
+            split["original_image_size"] = x.shape[-2:]
+            return first_stage_patched(self.first_stage_model.encode, x, split, df=split["vqf"])
         return self.first_stage_model.encode(x)
 
     def get_first_stage_encoding(self, encoder_posterior):
@@ -434,18 +519,29 @@ class LatentDiffusion(_Base):
             assert y is not None and y.dim() == 1 and cat is None, "conditioning_key 'adm': cond = class labels (B,)"
         ncat = 0 if cat is None else cat.shape[1]
         L_ctx = 0 if ctx is None else ctx.shape[1]
-        pg = unet.program(b, shape[2], shape[3], L_ctx, ncat)
-        if L_ctx:
-            pg.inputs["context"].copy_(ctx.reshape(b * L_ctx, -1))
-        if ncat:
-            pg.inputs["c_concat"].copy_(cat)
-        if y is not None:
-            pg.inputs["y_emb"].copy_(unet.label_emb.weight.detach().float()[y.to(dev, torch.int64)])
-        pg.ctx_program.run()
-        x_buf, t_buf, eps = pg.inputs["x"], pg.inputs["t"], pg.outputs["eps"]
+        y_emb = None if y is None else unet.label_emb.weight.detach().float()[y.to(dev, torch.int64)]
+        if hasattr(self, "split_input_params"):
+            # patch-wise (ddpm.py:904-986): the latent lives in a full-size buffer; one step = unfold -> the program at batch
+            # L*b -> fold -> the posterior update on the full-size tensors.  Conditioning crops are written once per run.
+            pe = self._patched_eval(b, shape[1], shape[2], shape[3], L_ctx, ncat)
+            pg = pe.pg
+            pe.set_cond(ctx, cat, y_emb)
+            x_buf, eps, run_net = pe.x, pe.eps, pe.run
+            loops = pe.loops.setdefault("ddpm", {})             # (never the plain loop's state of the same program)
+        else:
+            pg = unet.program(b, shape[2], shape[3], L_ctx, ncat)
+            if L_ctx:
+                pg.inputs["context"].copy_(ctx.reshape(b * L_ctx, -1))
+            if ncat:
+                pg.inputs["c_concat"].copy_(cat)
+            if y_emb is not None:
+                pg.inputs["y_emb"].copy_(y_emb)
+            pg.ctx_program.run()
+            x_buf, eps, run_net = pg.inputs["x"], pg.outputs["eps"], pg.run
+            loops = pg.__dict__.setdefault("_ddpm_loops", {})   # (the state lives on the program and dies with it, like ddim.py's)
+        t_buf = pg.inputs["t"]                                  # (patch-wise: L*b entries, all the current timestep)
         tab, logvar = self._ddpm_device_tables()
         key = (timesteps, bool(use_graph), noise is None)
-        loops = pg.__dict__.setdefault("_ddpm_loops", {})       # (the state lives on the program and dies with it, like ddim.py's)
         st = loops.get(key)
         if st is None:
             st = dict(nz=torch.empty_like(img0), idx=torch.zeros(1, dtype=torch.int32, device=dev),
@@ -463,11 +559,11 @@ class LatentDiffusion(_Base):
         def one_step(draw=True):
             if draw:
                 nz.normal_()
-            pg.run()
+            run_net()
             stream = torch.cuda.current_stream().cuda_stream
             L.check(lib.ldmk_ddpm_step(x_buf.data_ptr(), eps.data_ptr(), nz.data_ptr(), tab.data_ptr(), logvar.data_ptr(),
                                        t_buf.data_ptr(), x_buf.data_ptr(), per, b, stream), "ldmk_ddpm_step")
-            L.check(lib.ldmk_advance_timestep(idx.data_ptr(), tt.data_ptr(), t_buf.data_ptr(), b, 1, self.num_timesteps,
+            L.check(lib.ldmk_advance_timestep(idx.data_ptr(), tt.data_ptr(), t_buf.data_ptr(), t_buf.numel(), 1, self.num_timesteps,
                                               stream), "ldmk_advance_timestep")
 
         reset()
@@ -851,6 +947,8 @@ class LatentDiffusion2Cond(LatentDiffusion):
 
     @torch.no_grad()
     def apply_model(self, x_noisy, t, cond12, cond34=None, return_ids=False):
+        if hasattr(self, "split_input_params"):
+            raise NotImplementedError("LatentDiffusion2Cond.apply_model: split_input_params (ddpm2cond.py:937-938 raises too)")
         c12 = cond12 if isinstance(cond12, (list, dict)) else [cond12]
         c34 = cond34 if isinstance(cond34, (list, dict)) or cond34 is None else [cond34]
         kwargs = dict(c12) if isinstance(c12, dict) else {"c_crossattn": c12}

@@ -142,6 +142,8 @@ _SIGS = {
                                  C.c_int, C.c_int, C.c_int, _fp]),
     "ldmk_advance_timestep": (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_int, C.c_int, _fp]),
     "ldmk_ddpm_step": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_longlong, C.c_int, _fp]),
+    "ldmk_patch_unfold": (C.c_int, [_fp, _fp] + [C.c_int] * 10 + [_fp]),
+    "ldmk_patch_fold": (C.c_int, [_fp, _fp, _fp, _fp] + [C.c_int] * 10 + [_fp]),
     "ldmk_vq_nearest": (C.c_int, [_fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
     "ldmk_permute3": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
     "ldmk_audio_attention": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp, _fp]),

@@ -770,3 +770,34 @@ def add_rowvec_(x2d, vec, rows_per_sample):
     rows, c = x2d.shape
     L.call("ldmk_add_rowvec", _ptr(x2d), _ptr(vec), vec.stride(0), rows, c, rows_per_sample, stream())
     return x2d
+
+
+# ------------------------------------------------------------------------------------------ patch-wise evaluation
+def patch_unfold(x, kh, kw, sh, sw, out=None):
+    """x (n,c,h,w) NCHW -> its overlapping crops as batch items (ly*lx*n, c, kh, kw), patch-major (torch.nn.Unfold's L order)."""
+    _chk(x, "patch_unfold")
+    n, c, h, w_ = x.shape
+    ly, lx = (h - kh) // sh + 1, (w_ - kw) // sw + 1
+    if out is None:
+        out = torch.empty(max(ly * lx, 0) * n, c, kh, kw, device=x.device, dtype=torch.float32)
+    _chk(out, "patch_unfold out")
+    assert out.numel() == max(ly * lx, 0) * n * c * kh * kw, "patch_unfold: out has the wrong size"
+    L.call("ldmk_patch_unfold", _ptr(x), _ptr(out), n, c, h, w_, kh, kw, sh, sw, ly, lx, stream())
+    return out
+
+
+def patch_fold(patches, weight, norm, n, sh, sw, out=None):
+    """patches (ly*lx*n, c, kh, kw) patch-major, weight (kh,kw,ly*lx), norm (h,w) -> the weighted overlap-add divided by norm,
+    (n,c,h,w).  Sums in ascending patch index, deterministic."""
+    for t, name in ((patches, "patch_fold patches"), (weight, "patch_fold weight"), (norm, "patch_fold norm")):
+        _chk(t, name)
+    c, kh, kw = patches.shape[1:]
+    h, w_ = norm.shape
+    ly, lx = (h - kh) // sh + 1, (w_ - kw) // sw + 1
+    assert patches.shape[0] == ly * lx * n and tuple(weight.shape) == (kh, kw, ly * lx), "patch_fold: shapes do not match the geometry"
+    if out is None:
+        out = torch.empty(n, c, h, w_, device=patches.device, dtype=torch.float32)
+    _chk(out, "patch_fold out")
+    assert out.numel() == n * c * h * w_, "patch_fold: out has the wrong size"
+    L.call("ldmk_patch_fold", _ptr(patches), _ptr(weight), _ptr(norm), _ptr(out), n, c, h, w_, kh, kw, sh, sw, ly, lx, stream())
+    return out

@@ -532,6 +532,25 @@ int ldmk_ddpm_step(const float* x, const float* eps, const float* noise, const f
                    const long long* t, float* x_prev, long long per_sample, int n, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Patch-wise evaluation (`split_input_params`, ddpm.py:565-652,716-753,828-859,904-986): the overlapping crops of an
+ * image larger than the network was trained at become BATCH ITEMS of one network call.
+ * ldmk_patch_unfold: x (n,c,h,w) NCHW -> patches (ly*lx*n, c, kh, kw), patch-major: item l*n + b with l = iy*lx + ix
+ *   (torch.nn.Unfold's L order, ddpm.py:914-917) holds x[b, :, iy*sh : iy*sh+kh, ix*sw : ix*sw+kw].  A pure copy.
+ * ldmk_patch_fold: out[b,c,y,x] = (sum_l patches[l*n+b, c, y-iy*sh, x-ix*sw] * weight[y-iy*sh][x-ix*sw][l]) / norm[y][x]
+ *   over the patches that cover (y,x) in ascending l (gather form: no atomics, one fixed order); each product is
+ *   rounded before it is added and the quotient is a correctly rounded division, as `fold(o * weighting) / normalization`
+ *   (ddpm.py:982-986).  weight: [kh][kw][ly*lx]; norm: [h][w] (the fold of the weights).
+ * Both: ly = (h-kh)/sh + 1, lx = (w-kw)/sw + 1, and the patches must tile the image exactly, (ly-1)*sh + kh == h
+ * (same along w) -- an uncovered pixel is 0/0 in the reference -- else LDMK_EINVAL.  16-byte accesses when w, kw, sw
+ * and the pointers are multiples of 4 floats, a scalar kernel otherwise.  The first stage folds at sizes already
+ * multiplied / divided by its downsampling factor; these kernels know nothing of it.
+ */
+int ldmk_patch_unfold(const float* x, float* patches, int n, int c, int h, int w, int kh, int kw, int sh, int sw, int ly,
+                      int lx, void* stream);
+int ldmk_patch_fold(const float* patches, const float* weight, const float* norm, float* out, int n, int c, int h, int w,
+                    int kh, int kw, int sh, int sw, int ly, int lx, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * VQ nearest-codebook lookup, taming/modules/vqvae/quantize.py:276-285:
  *   idx = argmin_j ( |z|^2 + |e_j|^2 - 2 z.e_j ), z_q = e[idx]; z, z_q NCHW [n][dim][hw].
  */
