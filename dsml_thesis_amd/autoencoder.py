@@ -1,11 +1,16 @@
-"""MI355X-native VQGAN first stage: drop-in for `ldm.models.autoencoder.VQModelInterface`
-(autoencoder.py:264-282) as the samplers use it -- `decode` (VQ lookup -> post_quant_conv ->
-Decoder, model.py:462-568) and `encode` (Encoder -> quant_conv, model.py:368-459).  Training-side
-members of the reference class (loss, optimisers, EMA of the VQGAN) are out of scope.
+"""MI355X-native first stages: drop-ins for the three classes `ldm.models.autoencoder` offers LatentDiffusion.
 
-Parameter tree and state-dict keys equal the reference's (`encoder.*`, `decoder.*`,
-`quantize.embedding.weight`, `quant_conv.*`, `post_quant_conv.*`).  Forward passes are launch
-programs over libldmk.so kernels (NHWC inside, NCHW at the boundary); no PyTorch fallback.
+`VQModelInterface` (autoencoder.py:264-282) as the samplers use it -- `decode` (VQ lookup -> post_quant_conv ->
+Decoder, model.py:462-568) and `encode` (Encoder -> quant_conv, model.py:368-459).
+`AutoencoderKL` (autoencoder.py:285-342): `encode` -> DiagonalGaussianDistribution over the moments the encoder's
+double-width head produces (one kernel, ldmk_conv3x3_moments), `decode` = post_quant_conv -> Decoder.
+`IdentityFirstStage` (autoencoder.py:426-443): pixels are the latents.
+Training-side members of the reference classes (loss, optimisers, EMA of the autoencoder) are out of scope.
+
+Parameter trees and state-dict keys equal the reference's (`encoder.*`, `decoder.*`, `quant_conv.*`,
+`post_quant_conv.*`, and `quantize.embedding.weight` for the VQ model).  Forward passes are launch programs over
+libldmk.so kernels (NHWC inside, NCHW at the boundary); no PyTorch fallback.  What the two autoencoders share --
+weight packing, the block emitters, the decoder program, the encoder trunk and the program cache -- is `_FirstStage`.
 """
 import math
 
@@ -14,6 +19,7 @@ import torch.nn as nn
 
 from . import lib as L
 from . import ops
+from .distributions import DiagonalGaussianDistribution
 from .engine import NetBuilder, Program
 from .unet import _Params, _Slots, _conv_params, _norm_params
 
@@ -149,21 +155,15 @@ class VectorQuantizer(nn.Module):
         return z_q
 
 
-class VQModelInterface(nn.Module):
-    def __init__(self, embed_dim, ddconfig=None, lossconfig=None, n_embed=None, ckpt_path=None, ignore_keys=[],
-                 image_key="image", colorize_nlabels=None, monitor=None, batch_resize_range=None,
-                 scheduler_config=None, lr_g_factor=1.0, remap=None, sane_index_shape=False, use_ema=False, **kw):
-        super().__init__()
-        ddconfig = dict(ddconfig)
-        self.embed_dim, self.n_embed, self.image_key = embed_dim, n_embed, image_key
-        self.ddconfig = ddconfig
-        self.encoder = Encoder(**ddconfig)
-        self.decoder = Decoder(**ddconfig)
-        self.quantize = VectorQuantizer(n_embed, embed_dim, beta=0.25, remap=remap, sane_index_shape=sane_index_shape)
-        self.quant_conv = _conv_params(ddconfig["z_channels"], embed_dim, 1)
-        self.post_quant_conv = _conv_params(embed_dim, ddconfig["z_channels"], 1)
-        if monitor is not None:
-            self.monitor = monitor
+class _FirstStage(nn.Module):
+    """What VQModelInterface and AutoencoderKL share: recipe-free initialisation, checkpoint loading, kernel-layout
+    weight packing, the ResnetBlock / AttnBlock emitters, the decoder program, the encoder trunk up to norm_out, and
+    the program cache.  A subclass registers its modules, then calls `_finish_init`."""
+
+    NARROW_KEYS = ()          # 3x3 weights that take the [9][cin][cout] boundary layout whatever their width
+    SKIP_INIT = ()            # parameters that keep their own initialisation
+
+    def _finish_init(self, ckpt_path, ignore_keys):
         self._init_weights()
         self._packed, self._pack_sig, self._programs = None, None, {}
         self.policy_batch = None
@@ -174,7 +174,7 @@ class VQModelInterface(nn.Module):
     def _init_weights(self):
         params = dict(self.named_parameters())
         for name, p in params.items():
-            if name == "quantize.embedding.weight":
+            if name in self.SKIP_INIT:
                 continue
             if p.dim() >= 2:
                 b = 1.0 / math.sqrt(p[0].numel())
@@ -205,13 +205,14 @@ class VQModelInterface(nn.Module):
     def pack_weights(self):
         dev = next(self.parameters()).device
         if dev.type != "cuda":
-            raise L.LdmkError("VQModelInterface: parameters must live on a GPU; there is no CPU path")
+            raise L.LdmkError(f"{type(self).__name__}: parameters must live on a GPU; there is no CPU path")
         sd = {k: v.detach().float().contiguous() for k, v in self.named_parameters()}
         P = {}
         for k, v in sd.items():
             if k.endswith(".weight") and v.dim() == 4:
                 if v.shape[2] == 3:
-                    narrow = v.shape[1] % 32 != 0 or v.shape[0] <= 4      # conv_in / conv_out at the latent / image boundary
+                    # conv_in / conv_out at the latent / image boundary (and the KL encoder's 6- or 8-channel moment head)
+                    narrow = v.shape[1] % 32 != 0 or v.shape[0] <= 4 or k in self.NARROW_KEYS
                     P[k] = ops.pack_conv3x3_narrow(v) if narrow else ops.pack_conv3x3(v)
                     if not narrow and v.shape[1] >= NetBuilder.WINO_MIN_CIN and k.endswith(("conv1.weight", "conv2.weight")):
                         P[k + "#wg"] = ops.pack_winograd(v)     # ResnetBlock convs wide enough for the Winograd route
@@ -287,13 +288,13 @@ class VQModelInterface(nn.Module):
         P, sd = self._packed, self._sd
         dev = next(self.parameters()).device
         pg = Program(dev)
-        zc = d.z_channels
-        z_in = pg.alloc(n, zc, h, w)
+        zc, ed = d.z_channels, self.embed_dim               # latents carry embed_dim channels, post_quant_conv -> z_channels
+        z_in = pg.alloc(n, ed, h, w)
         pg.inputs = dict(z=z_in)
-        idx = pg.alloc(n * h * w, dtype=torch.int32)
+        idx = pg.alloc(n * h * w, dtype=torch.int32) if hasattr(self, "quantize") else None
         zcur = z_in
         if quantize:
-            zq = pg.alloc(n, zc, h, w)
+            zq = pg.alloc(n, ed, h, w)
             pg.add("ldmk_vq_nearest", z_in.data_ptr(), sd["quantize.embedding.weight"].data_ptr(), zq.data_ptr(),
                    idx.data_ptr(), n, h * w, self.embed_dim, self.n_embed)
             zcur = zq
@@ -334,10 +335,12 @@ class VQModelInterface(nn.Module):
         img = pg.alloc(n, d.out_ch, ch_, cw_)
         pg.add("ldmk_conv3x3_out", x.data_ptr(), coef.data_ptr(), P["decoder.conv_out.weight"].data_ptr(),
                sd["decoder.conv_out.bias"].data_ptr(), img.data_ptr(), n, ch_, cw_, d._final_ch, d.out_ch)
-        pg.outputs = dict(image=img, indices=idx)
+        pg.outputs = dict(image=img) if idx is None else dict(image=img, indices=idx)
         return pg
 
-    def _build_encode(self, n, H, W_):
+    def _encode_trunk(self, n, H, W_):
+        """Encoder up to norm_out (model.py:434-456): -> (program, builder, NHWC features, GroupNorm coefficient planes,
+        h, w).  The subclass appends its head and names the outputs."""
         e = self.encoder
         P, sd = self._packed, self._sd
         dev = next(self.parameters()).device
@@ -373,14 +376,7 @@ class VQModelInterface(nn.Module):
         step(self._attn, "encoder.mid.attn_1.", e.mid.attn_1, ch_, cw_)
         step(self._resnet_block, "encoder.mid.block_2.", e.mid.block_2, ch_, cw_)
         coef = nb.gn(x, None, ch_ * cw_, sd["encoder.norm_out.weight"], sd["encoder.norm_out.bias"], 1e-6)
-        hz = pg.alloc(n, e.z_out, ch_, cw_)
-        pg.add("ldmk_conv3x3_out", x.data_ptr(), coef.data_ptr(), P["encoder.conv_out.weight"].data_ptr(),
-               sd["encoder.conv_out.bias"].data_ptr(), hz.data_ptr(), n, ch_, cw_, e._final_ch, e.z_out)
-        z = pg.alloc(n, self.embed_dim, ch_, cw_)
-        pg.add("ldmk_conv1x1_nchw", hz.data_ptr(), P["quant_conv.weight"].data_ptr(), sd["quant_conv.bias"].data_ptr(),
-               z.data_ptr(), n, ch_ * cw_, e.z_out, self.embed_dim)
-        pg.outputs = dict(z=z)
-        return pg
+        return pg, nb, x, coef, ch_, cw_
 
     def _program(self, kind, *key):
         self._ensure()
@@ -389,6 +385,38 @@ class VQModelInterface(nn.Module):
         if pg is None:
             pg = self._build_decode(*key) if kind == "dec" else self._build_encode(*key)
             self._programs[k] = pg
+        return pg
+
+
+class VQModelInterface(_FirstStage):
+    SKIP_INIT = ("quantize.embedding.weight",)
+
+    def __init__(self, embed_dim, ddconfig=None, lossconfig=None, n_embed=None, ckpt_path=None, ignore_keys=[],
+                 image_key="image", colorize_nlabels=None, monitor=None, batch_resize_range=None,
+                 scheduler_config=None, lr_g_factor=1.0, remap=None, sane_index_shape=False, use_ema=False, **kw):
+        super().__init__()
+        ddconfig = dict(ddconfig)
+        self.embed_dim, self.n_embed, self.image_key = embed_dim, n_embed, image_key
+        self.ddconfig = ddconfig
+        self.encoder = Encoder(**ddconfig)
+        self.decoder = Decoder(**ddconfig)
+        self.quantize = VectorQuantizer(n_embed, embed_dim, beta=0.25, remap=remap, sane_index_shape=sane_index_shape)
+        self.quant_conv = _conv_params(ddconfig["z_channels"], embed_dim, 1)
+        self.post_quant_conv = _conv_params(embed_dim, ddconfig["z_channels"], 1)
+        if monitor is not None:
+            self.monitor = monitor
+        self._finish_init(ckpt_path, ignore_keys)
+
+    def _build_encode(self, n, H, W_):
+        e, P, sd = self.encoder, self._packed, self._sd
+        pg, nb, x, coef, ch_, cw_ = self._encode_trunk(n, H, W_)
+        hz = pg.alloc(n, e.z_out, ch_, cw_)
+        pg.add("ldmk_conv3x3_out", x.data_ptr(), coef.data_ptr(), P["encoder.conv_out.weight"].data_ptr(),
+               sd["encoder.conv_out.bias"].data_ptr(), hz.data_ptr(), n, ch_, cw_, e._final_ch, e.z_out)
+        z = pg.alloc(n, self.embed_dim, ch_, cw_)
+        pg.add("ldmk_conv1x1_nchw", hz.data_ptr(), P["quant_conv.weight"].data_ptr(), sd["quant_conv.bias"].data_ptr(),
+               z.data_ptr(), n, ch_ * cw_, e.z_out, self.embed_dim)
+        pg.outputs = dict(z=z)
         return pg
 
     # ---- public surface (autoencoder.py:269-282) ------------------------------------------------------------
@@ -415,3 +443,90 @@ class VQModelInterface(nn.Module):
 
     def forward(self, x):
         return self.decode(self.encode(x))
+
+
+class AutoencoderKL(_FirstStage):
+    """autoencoder.py:285-342 as LatentDiffusion uses it.  The encoder ends in a 3x3 convolution to 2*z_channels moment
+    channels and a 1x1 `quant_conv` to 2*embed_dim: both run in one kernel (ldmk_conv3x3_moments), which is built for up to
+    8 channels on either side -- z_channels, embed_dim <= 4, i.e. the KL-f4 and KL-f8 autoencoders."""
+
+    NARROW_KEYS = ("encoder.conv_out.weight",)
+    MAX_Z = 4
+
+    def __init__(self, ddconfig, lossconfig, embed_dim, ckpt_path=None, ignore_keys=[], image_key="image",
+                 colorize_nlabels=None, monitor=None):
+        super().__init__()
+        ddconfig = dict(ddconfig)
+        assert ddconfig["double_z"]
+        zc = ddconfig["z_channels"]
+        if zc > self.MAX_Z or embed_dim > self.MAX_Z:
+            raise NotImplementedError(f"AutoencoderKL: z_channels={zc}, embed_dim={embed_dim}: the moment head "
+                                      f"(ldmk_conv3x3_moments) is built for z_channels <= {self.MAX_Z} and embed_dim <= "
+                                      f"{self.MAX_Z} (KL-f4 / KL-f8); wider heads (KL-f16 / KL-f32) are not built")
+        self.embed_dim, self.image_key, self.ddconfig = embed_dim, image_key, ddconfig
+        self.encoder = Encoder(**ddconfig)
+        self.decoder = Decoder(**ddconfig)
+        self.quant_conv = _conv_params(2 * zc, 2 * embed_dim, 1)
+        self.post_quant_conv = _conv_params(embed_dim, zc, 1)
+        if colorize_nlabels is not None:
+            assert type(colorize_nlabels) == int
+            self.register_buffer("colorize", torch.randn(3, colorize_nlabels, 1, 1))
+        if monitor is not None:
+            self.monitor = monitor
+        self._finish_init(ckpt_path, ignore_keys)
+
+    def _build_encode(self, n, H, W_):
+        e, P, sd = self.encoder, self._packed, self._sd
+        pg, nb, x, coef, ch_, cw_ = self._encode_trunk(n, H, W_)
+        moments = pg.alloc(n, 2 * self.embed_dim, ch_, cw_)
+        pg.add("ldmk_conv3x3_moments", x.data_ptr(), coef.data_ptr(), P["encoder.conv_out.weight"].data_ptr(),
+               sd["encoder.conv_out.bias"].data_ptr(), P["quant_conv.weight"].data_ptr(), sd["quant_conv.bias"].data_ptr(),
+               moments.data_ptr(), n, ch_, cw_, e._final_ch, e.z_out, 2 * self.embed_dim)
+        pg.outputs = dict(moments=moments)
+        return pg
+
+    # ---- public surface (autoencoder.py:324-342) ------------------------------------------------------------
+    @torch.no_grad()
+    def encode(self, x):
+        if not x.is_cuda:
+            raise L.LdmkError("AutoencoderKL.encode: CUDA tensors only (no CPU fallback)")
+        n, _, H, W_ = x.shape
+        pg = self._program("enc", n, H, W_)
+        pg.inputs["x"].copy_(x)
+        pg.run()
+        return DiagonalGaussianDistribution(pg.outputs["moments"].clone())
+
+    @torch.no_grad()
+    def decode(self, z):
+        if not z.is_cuda:
+            raise L.LdmkError("AutoencoderKL.decode: CUDA tensors only (no CPU fallback)")
+        n, _, hh, ww = z.shape
+        pg = self._program("dec", n, hh, ww, False)
+        pg.inputs["z"].copy_(z)
+        pg.run()
+        return pg.outputs["image"].clone()
+
+    def forward(self, input, sample_posterior=True):
+        posterior = self.encode(input)
+        z = posterior.sample() if sample_posterior else posterior.mode()
+        return self.decode(z), posterior
+
+
+class IdentityFirstStage(nn.Module):
+    """autoencoder.py:426-443: pixel-space diffusion, the first stage passes everything through.  No parameters, no launches."""
+
+    def __init__(self, *args, vq_interface=False, **kwargs):
+        super().__init__()
+        self.vq_interface = vq_interface
+
+    def encode(self, x, *args, **kwargs):
+        return x
+
+    def decode(self, x, *args, **kwargs):
+        return x
+
+    def quantize(self, x, *args, **kwargs):
+        return (x, None, [None, None, None]) if self.vq_interface else x
+
+    def forward(self, x, *args, **kwargs):
+        return x

@@ -289,7 +289,7 @@ class DDIMSampler(object):
                                     torch.cuda.current_stream().cuda_stream)
             L.check(rc, "ldmk_ddim_step")
             if quantize_denoised:                          # x_prev = sqrt(a_prev) Q(pred_x0) + dir_xt + noise (ddim.py:194-202)
-                q = self.model.first_stage_model.quantize(pred_x0)[0]
+                q = self.model._quantize_denoised(pred_x0)
                 img.add_(torch.sqrt(a_prev) * (q - pred_x0))
                 pred_x0.copy_(q)
             if cfg:
@@ -376,7 +376,7 @@ class DDIMSampler(object):
                x_prev.data_ptr(), pred_x0.data_ptr(), x[0].numel(), b, 0, 0, 0, 0, 0,
                torch.cuda.current_stream().cuda_stream)
         if quantize_denoised:                                # ddim.py:195-196
-            q = self.model.first_stage_model.quantize(pred_x0)[0]
+            q = self.model._quantize_denoised(pred_x0)
             x_prev = x_prev + torch.sqrt(table[int(index), 1]) * (q - pred_x0)
             pred_x0 = q
         return x_prev, pred_x0

@@ -17,6 +17,7 @@ import torch.nn as nn
 
 from . import lib as L
 from . import schedule as S_
+from .distributions import DiagonalGaussianDistribution
 from .unet import rerun_if_flags_tripped
 from .util import instantiate_from_config
 
@@ -348,29 +349,74 @@ class LatentDiffusion(_Base):
     # ---- first stage ---------------------------------------------------------------------------------
     @torch.no_grad()
     def decode_first_stage(self, z, predict_cids=False, force_not_quantize=False):
-        """ddpm.py:706-764 -> VQModelInterface.decode."""
+        """ddpm.py:706-764 -> first_stage_model.decode; `force_not_quantize` goes to a VQModelInterface only (:737-764)."""
         if predict_cids:
             raise NotImplementedError("decode_first_stage(predict_cids=True) is unused on the sampling path")
         z = 1. / self.scale_factor * z
+        from .autoencoder import VQModelInterface
+        fs = self.first_stage_model
+        dec = (lambda c: fs.decode(c, force_not_quantize=force_not_quantize)) if isinstance(fs, VQModelInterface) else fs.decode
         split = getattr(self, "split_input_params", None)
-        if split is not None and split["patch_distributed_vq"]:           # ddpm.py:716-753: every crop is quantised on its own
+        if split is not None and split["patch_distributed_vq"]:           # ddpm.py:716-753: every crop is decoded on its own
             from .patches import first_stage_patched
-            return first_stage_patched(lambda c: self.first_stage_model.decode(c, force_not_quantize=force_not_quantize), z, split,
-                                       uf=split["vqf"])
-        return self.first_stage_model.decode(z, force_not_quantize=force_not_quantize)
+            return first_stage_patched(dec, z, split, uf=split["vqf"])
+        return dec(z)
 
     @torch.no_grad()
     def encode_first_stage(self, x):
         """ddpm.py:826-864 -> VQModelInterface.encode (no quantisation)."""
         split = getattr(self, "split_input_params", None)
         if split is not None and split["patch_distributed_vq"]:           # ddpm.py:828-859
+            from .autoencoder import AutoencoderKL
+            if isinstance(self.first_stage_model, AutoencoderKL):
+                raise NotImplementedError("encode_first_stage: split_input_params with an AutoencoderKL first stage: the crops' "
+                                          "posteriors cannot be folded (the reference fails there too, stacking distributions, "
+                                          "ddpm.py:851)")
             from .patches import first_stage_patched
             split["original_image_size"] = x.shape[-2:]
             return first_stage_patched(self.first_stage_model.encode, x, split, df=split["vqf"])
         return self.first_stage_model.encode(x)
 
-    def get_first_stage_encoding(self, encoder_posterior):
-        return self.scale_factor * encoder_posterior
+    def get_first_stage_encoding(self, encoder_posterior, noise=None):
+        """ddpm.py:541-548: a posterior is sampled, a tensor passes through; times scale_factor.  A Python-float scale_factor
+        rides in the sampling kernel; the `scale_by_std` buffer multiplies on the device.  `noise`: the posterior's normal
+        draw (parity with a seeded reference run), default a fresh one."""
+        if isinstance(encoder_posterior, DiagonalGaussianDistribution):
+            if isinstance(self.scale_factor, float):
+                return encoder_posterior.sample(noise=noise, scale=self.scale_factor)
+            z = encoder_posterior.sample(noise=noise)
+        elif isinstance(encoder_posterior, torch.Tensor):
+            z = encoder_posterior
+        else:
+            raise NotImplementedError(f"encoder_posterior of type '{type(encoder_posterior)}' not yet implemented")
+        return self.scale_factor * z
+
+    def _quantize_denoised(self, x_recon):
+        """`quantize_denoised=True` (ddpm.py:1073-1074, ddim.py:190-191) needs a first stage with a codebook."""
+        quantize = getattr(self.first_stage_model, "quantize", None)
+        if quantize is None:
+            raise NotImplementedError(f"quantize_denoised=True: the first stage ({type(self.first_stage_model).__name__}) "
+                                      "has no `quantize`; only a VQ first stage can snap the x0 estimate to its codebook")
+        return quantize(x_recon)[0]
+
+    @torch.no_grad()
+    def on_train_batch_start(self, batch, batch_idx, dataloader_idx=0):
+        """ddpm.py:476-490: with `scale_by_std`, the very first batch of a fresh run sets scale_factor to 1 / std of its
+        latents.  Lightning calls this hook; without a Lightning trainer `training_step` does."""
+        if not self.scale_by_std or batch_idx != 0 or self.restarted_from_ckpt or getattr(self, "_std_rescaled", False):
+            return
+        if int(getattr(self, "current_epoch", 0) or 0) != 0 or int(getattr(self, "global_step", 0) or 0) != 0:
+            return
+        assert self.scale_factor == 1., "rather not use custom rescaling and std-rescaling simultaneously"
+        print("### USING STD-RESCALING ###")
+        x = batch[self.first_stage_key]
+        x = (x[..., None] if x.dim() == 3 else x).permute(0, 3, 1, 2).contiguous().float().to(self.device)
+        z = self.get_first_stage_encoding(self.encode_first_stage(x)).detach()
+        del self.scale_factor
+        self.register_buffer("scale_factor", 1. / z.flatten().std())      # once per run: plain torch on the device
+        self._std_rescaled = True
+        print(f"setting self.scale_factor to {self.scale_factor}")
+        print("### USING STD-RESCALING ###")
 
     # ---- ancestral sampler -----------------------------------------------------------------------------
     def _ddpm_device_tables(self):
@@ -421,7 +467,7 @@ class LatentDiffusion(_Base):
         if clip_denoised:
             x_recon = x_recon.clamp(-1., 1.)
         if quantize_denoised:
-            x_recon = self.first_stage_model.quantize(x_recon)[0]
+            x_recon = self._quantize_denoised(x_recon)
         out = self.q_posterior(x_start=x_recon, x_t=x, t=t)
         return out + (x_recon,) if return_x0 else out
 
@@ -456,7 +502,7 @@ class LatentDiffusion(_Base):
         if clip_denoised:
             x_recon = x_recon.clamp(-1., 1.)
         if quantize_denoised:
-            x_recon = self.first_stage_model.quantize(x_recon)[0]
+            x_recon = self._quantize_denoised(x_recon)
         mean = ex(self.posterior_mean_coef1) * x_recon + ex(self.posterior_mean_coef2) * x                # q_posterior :221-228
         nonzero = (1 - (t == 0).float()).view(-1, 1, 1, 1)
         out = mean + nonzero * (0.5 * ex(self.posterior_log_variance_clipped)).exp() * noise
@@ -753,6 +799,8 @@ class LatentDiffusion(_Base):
 
     def training_step(self, batch, batch_idx=0):
         """ddpm.py:341-358 with manual optimisation: batch -> (latents, condition) -> one full step."""
+        if self.scale_by_std:      # Lightning's loop has already called the hook (it runs once); a plain loop has not
+            self.on_train_batch_start(batch, batch_idx, 0)
         z, c = self.get_input(batch, self.first_stage_key)
         lr = float(getattr(self, "learning_rate", 1e-4))
         if getattr(self, "lr_schedule", None) is not None:

@@ -26,6 +26,10 @@ class LatentDiffusionCLIP(LatentDiffusion):
         if eta != 0.0 or quantize_x0 or score_corrector is not None:
             raise NotImplementedError("LatentDiffusionCLIP: eta = 0, no x0 quantisation, no score corrector (shipped settings)")
         super().__init__(first_stage_config, cond_stage_config, **kwargs)
+        from .autoencoder import VQModelInterface
+        if not isinstance(self.first_stage_model, VQModelInterface):
+            raise NotImplementedError(f"{type(self).__name__}: the fine-tune decodes differentiably through a VQ first stage; "
+                                      f"{type(self.first_stage_model).__name__} is not built for it")
         self.strength, self.num_train_steps, self.num_test_steps = strength, num_train_steps, num_test_steps
         self.unconditional_guidance_scale = unconditional_guidance_scale
         self.cls_loss_w, self.clip_loss_w, self.id_loss_w, self.l2_loss_w = cls_loss_w, clip_loss_w, id_loss_w, l2_loss_w

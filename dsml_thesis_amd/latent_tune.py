@@ -32,6 +32,10 @@ class LatentDiffusionTune(LatentDiffusion2Cond):
         assert concat_mode is False
         super().__init__(first_stage_config, cond_stage_config_1, cond_stage_config_2, cond_stage_trainable=cond_stage_trainable,
                          concat_mode=concat_mode, conditioning_key=conditioning_key, **kwargs)
+        from .autoencoder import VQModelInterface
+        if not isinstance(self.first_stage_model, VQModelInterface):
+            raise NotImplementedError(f"{type(self).__name__}: the fine-tune decodes differentiably through a VQ first stage; "
+                                      f"{type(self.first_stage_model).__name__} is not built for it")
         self.lr_loss_w, self.start_lr_loss = lr_loss_w, start_lr_loss
         self.lip_loss_func = None                                                   # plugged in by the caller
         self.num_tune_steps, self.tune_eta = num_tune_steps, tune_eta               # make_schedule(8, ddim_eta=1.0), :533

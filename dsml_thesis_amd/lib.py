@@ -144,6 +144,8 @@ _SIGS = {
     "ldmk_ddpm_step": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_longlong, C.c_int, _fp]),
     "ldmk_patch_unfold": (C.c_int, [_fp, _fp] + [C.c_int] * 10 + [_fp]),
     "ldmk_patch_fold": (C.c_int, [_fp, _fp, _fp, _fp] + [C.c_int] * 10 + [_fp]),
+    "ldmk_conv3x3_moments": (C.c_int, [_fp] * 7 + [C.c_int] * 6 + [_fp]),
+    "ldmk_gauss_posterior": (C.c_int, [_fp, _fp, C.c_float, _fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, _fp]),
     "ldmk_vq_nearest": (C.c_int, [_fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
     "ldmk_permute3": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
     "ldmk_audio_attention": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp, _fp]),

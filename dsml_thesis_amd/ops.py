@@ -748,6 +748,36 @@ def conv1x1_nchw(x, w, bias, out=None):
     return out
 
 
+def conv3x3_moments(x, coef, w3p, b3, w1, b1, out=None):
+    """KL moment head: NHWC (n,h,w,cin) -> GN+SiLU -> 3x3 conv to c2z -> 1x1 conv to c2e -> NCHW (n,c2e,h,w).
+    w3p: [9*cin][c2z] (pack_conv3x3_narrow); w1: [c2e][c2z]."""
+    n, h, w_, cin = x.shape
+    c2z, c2e = w3p.shape[1], w1.shape[0]
+    if out is None:
+        out = torch.empty(n, c2e, h, w_, device=x.device, dtype=torch.float32)
+    L.call("ldmk_conv3x3_moments", _ptr(x), _ptr(coef), _ptr(w3p), _ptr(b3), _ptr(w1), _ptr(b1), _ptr(out), n, h, w_, cin,
+           c2z, c2e, stream())
+    return out
+
+
+def gauss_posterior(moments, noise=None, scale=1.0, logvar=False, std=False, var=False, z=False):
+    """Diagonal-Gaussian posterior over moments (n,2e,h,w): the requested outputs, each (n,e,h,w), as a dict
+    (ldmk_gauss_posterior).  z = scale * (mean + std * noise), or scale * mean without noise."""
+    _chk(moments, "gauss_posterior")
+    _chk(noise, "gauss_posterior")
+    n, c2, h, w_ = moments.shape
+    if c2 % 2:
+        raise L.LdmkError(f"gauss_posterior: moments need an even channel count, got {c2}")
+    e = c2 // 2
+    if noise is not None and tuple(noise.shape) != (n, e, h, w_):
+        raise L.LdmkError(f"gauss_posterior: noise {tuple(noise.shape)} does not match the mean {(n, e, h, w_)}")
+    outs = {k: torch.empty(n, e, h, w_, device=moments.device, dtype=torch.float32)
+            for k, want in (("logvar", logvar), ("std", std), ("var", var), ("z", z)) if want}
+    L.call("ldmk_gauss_posterior", _ptr(moments), _ptr(noise), float(scale), _ptr(outs.get("logvar")), _ptr(outs.get("std")),
+           _ptr(outs.get("var")), _ptr(outs.get("z")), n, e, h * w_, stream())
+    return outs
+
+
 def vq_nearest(z, codebook, zq=None, idx=None):
     n, dim, h, w_ = z.shape
     if zq is None:

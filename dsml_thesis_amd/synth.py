@@ -30,6 +30,11 @@ VQ_F4 = dict(embed_dim=3, n_embed=16384,
 VQ_F4_256 = dict(embed_dim=4, n_embed=16384,
                  ddconfig=dict(double_z=False, z_channels=4, resolution=256, in_channels=3, out_ch=3, ch=128,
                                ch_mult=[1, 2, 4], num_res_blocks=2, attn_resolutions=[64], dropout=0.0))
+# KL-regularised first stages (ldm.models.autoencoder.AutoencoderKL): KL-f4 with the VQ-f4 trunk, and a narrow four-level KL-f8
+KL_F4 = dict(embed_dim=3, ddconfig=dict(VQ_F4["ddconfig"], double_z=True))
+KL_F8_SMALL = dict(embed_dim=4,
+                   ddconfig=dict(double_z=True, z_channels=4, resolution=64, in_channels=3, out_ch=3, ch=32, ch_mult=[1, 2, 2, 4],
+                                 num_res_blocks=1, attn_resolutions=[], dropout=0.0))
 SCHEDULE = dict(timesteps=1000, linear_start=0.0015, linear_end=0.0205)
 
 
@@ -101,6 +106,26 @@ def tf_config(seq_len=17):
         num_timesteps_cond=1, cond_stage_key_1="class_label", cond_stage_key_2="audio", cond_stage_trainable=True,
         conditioning_key="crossattn", image_size=32, channels=3, first_stage_key="image", log_every_t=200,
         monitor="val_loss_ema", **SCHEDULE)
+
+
+def kl_config(unet=None, kl=None, scale_factor=0.18215, scale_by_std=False):
+    """fr_config with an AutoencoderKL first stage (the `scale_factor` the published KL checkpoints ship with)."""
+    kl = kl or KL_F4
+    cfg = fr_config(unet)
+    cfg.update(first_stage_config=dict(target="ldm.models.autoencoder.AutoencoderKL",
+                                       params=dict(embed_dim=kl["embed_dim"], ddconfig=dict(kl["ddconfig"]),
+                                                   lossconfig=dict(target="torch.nn.Identity"))),
+               scale_factor=scale_factor, scale_by_std=scale_by_std)
+    return cfg
+
+
+def make_kl_model(gain=1.0, scale_factor=0.18215, unet=None, kl=None, scale_by_std=False, device="cuda"):
+    from .ddpm import LatentDiffusion
+    m = LatentDiffusion(**kl_config(unet, kl, scale_factor, scale_by_std))
+    load_recipe(m.model.diffusion_model, gain=gain)
+    load_recipe(m.first_stage_model)
+    load_recipe(m.cond_stage_model)
+    return m.to(device).eval()
 
 
 def make_fr_model(gain=1.0, unet=None, vq=None, device="cuda"):

@@ -7,6 +7,8 @@ import importlib
 TARGET_MAP = {
     "ldm.modules.diffusionmodules.openaimodel.UNetModel": "dsml_thesis_amd.unet.UNetModel",
     "ldm.models.autoencoder.VQModelInterface": "dsml_thesis_amd.autoencoder.VQModelInterface",
+    "ldm.models.autoencoder.AutoencoderKL": "dsml_thesis_amd.autoencoder.AutoencoderKL",
+    "ldm.models.autoencoder.IdentityFirstStage": "dsml_thesis_amd.autoencoder.IdentityFirstStage",
     "ldm.models.diffusion.ddpm.LatentDiffusion": "dsml_thesis_amd.ddpm.LatentDiffusion",
     "ldm.models.diffusion.ddpm2cond.LatentDiffusion": "dsml_thesis_amd.ddpm.LatentDiffusion2Cond",
     "ldm.models.diffusion.ddpm2condtune.LatentDiffusion": "dsml_thesis_amd.latent_tune.LatentDiffusionTune",

@@ -532,6 +532,25 @@ int ldmk_ddpm_step(const float* x, const float* eps, const float* noise, const f
                    const long long* t, float* x_prev, long long per_sample, int n, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * KL-regularised first stage (autoencoder.py:285-342, distributions.py:24-62).
+ * ldmk_conv3x3_moments: the encoder's moment head in one launch -- GroupNorm+SiLU prologue (coef planes, NULL: none)
+ *   -> 3x3 pad 1 conv cin -> c2z (Encoder.conv_out with double_z) -> 1x1 conv c2z -> c2e (quant_conv), both biases
+ *   (either may be NULL); NHWC input -> NCHW `moments` (n, c2e, h, w).  w3: [9][cin][c2z] (ldmk_conv3x3_out's layout),
+ *   w1: [c2e][c2z].  c2z and c2e are each one of 2, 4, 6, 8 (z_channels, embed_dim <= 4), cin a multiple of 4, else
+ *   LDMK_EINVAL before any launch.  The 3x3 sums run in ldmk_conv3x3_out's order and never leave registers; one fixed
+ *   summation order, no atomics.
+ * ldmk_gauss_posterior: elementwise over moments (n, 2e, hw) = [mean | log-variance] on the channel axis.  Writes any
+ *   subset of (NULL skips an output; each is (n, e, hw)):
+ *     logvar = clamp(log-variance, -30, 20), std = exp(logvar / 2), var = exp(logvar),
+ *     z = scale * (mean + std * noise), or scale * mean when noise is NULL.
+ *   exp is the accurate expf.  16-byte accesses when e*hw and every pointer are multiples of 4 floats, scalar otherwise.
+ */
+int ldmk_conv3x3_moments(const float* x, const float* coef, const float* w3, const float* b3, const float* w1,
+                         const float* b1, float* out, int n, int h, int w_, int cin, int c2z, int c2e, void* stream);
+int ldmk_gauss_posterior(const float* moments, const float* noise, float scale, float* logvar, float* std_, float* var,
+                         float* z, int n, int e, int hw, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Patch-wise evaluation (`split_input_params`, ddpm.py:565-652,716-753,828-859,904-986): the overlapping crops of an
  * image larger than the network was trained at become BATCH ITEMS of one network call.
  * ldmk_patch_unfold: x (n,c,h,w) NCHW -> patches (ly*lx*n, c, kh, kw), patch-major: item l*n + b with l = iy*lx + ix
