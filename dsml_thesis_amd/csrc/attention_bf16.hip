@@ -1426,7 +1426,7 @@ extern "C" int ldmk_attn_self_x3p_ps(const float* qkv, void* kv_scratch, float* 
   hipLaunchKernelGGL(attn_kv_split_kernel, dim3(ntiles, heads, n), dim3(256), 0, st, qkv, reinterpret_cast<unsigned char*>(kv_scratch), tokens, heads);
   // 64 queries per wave from X3P_QB2_MIN_TOKENS tokens (below, the grid of 256-query workgroups no longer fills the chip);
   // LDMK_ATTN_QB = 1 | 2 pins the form (measurements).  The result does not depend on it, bit for bit.
-  static const int qb_env = [] { const char* e = getenv("LDMK_ATTN_QB"); return e ? atoi(e) : 0; }();
+  const int qb_env = ldmk::switch_value(ldmk::SW_ATTN_QB);
   const int qb = qb_env == 1 || qb_env == 2 ? qb_env : (tokens >= X3P_QB2_MIN_TOKENS ? 2 : 1);
   if (qb == 2)
     hipLaunchKernelGGL(attn_x3p_fwd_kernel<2>, dim3((tokens + 255) / 256, heads, n), dim3(256), 0, st, qkv,
@@ -1478,15 +1478,15 @@ static int attn_self_h2_any(const float* qkv, void* kv_scratch, float* out, void
   if (prepass)
     hipLaunchKernelGGL(attn_kv_split_h2_kernel, dim3(ntiles, heads, n), dim3(256), 0, st, qkv, reinterpret_cast<unsigned char*>(kv_scratch), tokens,
                        heads, range_flag);
-  static const int qb_env = [] { const char* e = getenv("LDMK_ATTN_QB"); return e ? atoi(e) : 0; }();
+  const int qb_env = ldmk::switch_value(ldmk::SW_ATTN_QB);
   const int qb = qb_env == 1 || qb_env == 2 ? qb_env : (tokens >= X3P_QB2_MIN_TOKENS ? 2 : 1);
-  static const int remap = [] { const char* e = getenv("LDMK_ATTN_XCD"); return e ? atoi(e) : 1; }();
+  const int remap = ldmk::switch_value(ldmk::SW_ATTN_XCD);
   const int gx = qb == 2 ? (tokens + 255) / 256 : (tokens + 127) / 128;
   // (grid.x = query tiles x heads, grid.y = samples: the kernel linearises and re-deals the ids over the XCDs itself)
   // the pipelined key loop with the lazy running maximum wherever every wave has whole tiles (two query blocks per wave, tokens a
   // multiple of 256).  LDMK_ATTN_PIPE=1: pipelined with the exact maximum per block (the same bits as the phase-separated loop),
   // LDMK_ATTN_PIPE=0: the phase-separated loop (A/B: profiles/r05_ab_attn_pipe.txt)
-  static const int pipe_env = [] { const char* e = getenv("LDMK_ATTN_PIPE"); return e ? atoi(e) : 2; }();
+  const int pipe_env = ldmk::switch_value(ldmk::SW_ATTN_PIPE);
 #define LDMK_ATTN_H2_LAUNCH(QB_, PIPE_, LAZY_)                                                                                                    \
   hipLaunchKernelGGL((attn_h2_fwd_kernel<QB_, PIPE_, LAZY_>), dim3(gx * heads, n), dim3(256), 0, st, qkv, reinterpret_cast<const unsigned char*>(kv_scratch), \
                      out, reinterpret_cast<unsigned char*>(out_ps), tokens, heads, scale, range_flag, gx, remap)

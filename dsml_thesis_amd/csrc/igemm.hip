@@ -1189,9 +1189,9 @@ static int launch_cfg_g(const ldmk_igemm_args& a, int splitk, float* ws, hipStre
   dim3 grid(tiles, splitk, a.batch > 1 ? a.batch : 1);
   auto k = igemm_kernel<TM, TN, WM, WN, WK, KS, DB, BT, BF, FG, ASP>;
   cfg_set_attr<TM, TN, WM, WN, WK, KS, DB, BT, BF, FG, ASP>();
-  static const int nfast_env = [] { const char* e = getenv("LDMK_IG_NFAST"); return e ? atoi(e) : 1; }();
+  const int nfast_env = switch_value(SW_IG_NFAST);
   // tall problems only (M >> N: activations x a weight matrix); weight-gradient-like or b_trans shapes keep the old order
-  static const int lean_env = [] { const char* e = getenv("LDMK_IG_LEAN"); return e ? atoi(e) : 1; }();      // (0: the general epilogue everywhere, A/B)
+  const int lean_env = switch_value(SW_IG_LEAN);      // (0: the general epilogue everywhere, A/B)
   const int nfast = (nfast_env && !a.b_trans && (a.N + BN - 1) / BN > 1 && (a.M + BM - 1) / BM >= 8 ? 1 : 0) | (lean_env ? 0 : 2);
   hipLaunchKernelGGL(k, grid, dim3(256), lds, st, a, splitk, ws, nfast);
   if (splitk > 1 && !a.splitk_counters && !a.raw_slabs) return launch_splitk_reduce(a, splitk, ws, st);

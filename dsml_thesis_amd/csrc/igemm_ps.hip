@@ -860,8 +860,8 @@ static int ps_launch(const ldmk_igemm_args& a, int splitk, float* ws, hipStream_
   const int tiles = ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN);
   const int dbg = ps_probe_bits();
   static_assert(!KV || (size_t)NWM * NWN * 32 * 33 * 4 <= lds, "V^T transpose scratch fits the ring");
-  static const int nfast_env = [] { const char* e = getenv("LDMK_PS_NFAST"); return e ? atoi(e) : 1; }();
-  static const int lean_env = [] { const char* e = getenv("LDMK_PS_LEAN"); return e ? atoi(e) : 1; }();     // (0: the general epilogue everywhere, A/B)
+  const int nfast_env = switch_value(SW_PS_NFAST);
+  const int lean_env = switch_value(SW_PS_LEAN);     // (0: the general epilogue everywhere, A/B)
   const int nfast = (nfast_env && (a.N + BN - 1) / BN > 1 && (a.M + BM - 1) / BM >= 8 ? 1 : 0) | (lean_env ? 0 : 2);   // (a few row tiles only: the old order)
   hipLaunchKernelGGL((igemm_ps_kernel<NWM, NWN, TM, TN, NS, TR, PL, KV>), dim3(tiles, splitk, a.batch > 1 ? a.batch : 1), dim3(64 * NWM * NWN), lds,
                      st, a, splitk, ws, dbg, nfast);
@@ -1083,8 +1083,8 @@ static int psc_launch(const ldmk_igemm_args& a, int splitk, float* ws, hipStream
     attr = true;
   }
   const int tiles = ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN);
-  static const int nfast_env = [] { const char* e = getenv("LDMK_PS_NFAST"); return e ? atoi(e) : 1; }();
-  static const int lean_env = [] { const char* e = getenv("LDMK_PS_LEAN"); return e ? atoi(e) : 1; }();
+  const int nfast_env = switch_value(SW_PS_NFAST);
+  const int lean_env = switch_value(SW_PS_LEAN);
   const int nfast = (nfast_env && (a.N + BN - 1) / BN > 1 && (a.M + BM - 1) / BM >= 8 ? 1 : 0) | (lean_env ? 0 : 2);
   hipLaunchKernelGGL((igemm_psc_kernel<NWM, NWN, TM, TN, TR>), dim3(tiles, splitk, 1), dim3(64 * NWM * NWN), lds, st, a, splitk, ws, nfast);
   if (splitk > 1 && !a.raw_slabs) return launch_splitk_reduce(a, splitk, ws, st);

@@ -4,6 +4,9 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdarg.h>
+#include <stdlib.h>
+#include <limits.h>
+#include <atomic>
 #include "../../include/ldmk.h"
 
 namespace ldmk {
@@ -37,6 +40,38 @@ inline int check_launch(const char* what) {
       return LDMK_ENOMEM;              \
     }                                  \
   } while (0)
+
+// The library's A/B switches (dsml_thesis_amd/switches.py, scope "library"), in ONE table: {name, default, ...}.  An entry reads
+// its environment variable once, at the first launch that consults it (atoi of the text; the default when it is unset), and
+// ldmk_switch_override (include/ldmk.h) can put another value in front of that -- between launches only: a launcher reads the
+// value on the host, the kernels never see the table.
+enum switch_id { SW_IG_NFAST, SW_IG_LEAN, SW_PS_NFAST, SW_PS_LEAN, SW_ATTN_QB, SW_ATTN_XCD, SW_ATTN_PIPE, SW_WGRAD_TR, SW_WINO_STAGED, SW_COUNT };
+struct switch_entry {
+  const char* name;
+  int dflt;
+  std::atomic<int> env;       // INT_MIN: not read yet
+  std::atomic<int> ovr;       // < 0: none
+};
+inline switch_entry* switch_table() {
+  static switch_entry t[SW_COUNT] = {
+      {"LDMK_IG_NFAST", 1, {INT_MIN}, {-1}},   {"LDMK_IG_LEAN", 1, {INT_MIN}, {-1}},  {"LDMK_PS_NFAST", 1, {INT_MIN}, {-1}},
+      {"LDMK_PS_LEAN", 1, {INT_MIN}, {-1}},    {"LDMK_ATTN_QB", 0, {INT_MIN}, {-1}},  {"LDMK_ATTN_XCD", 1, {INT_MIN}, {-1}},
+      {"LDMK_ATTN_PIPE", 2, {INT_MIN}, {-1}},  {"LDMK_WGRAD_TR", 1, {INT_MIN}, {-1}}, {"LDMK_WINO_STAGED", 1, {INT_MIN}, {-1}},
+  };
+  return t;
+}
+inline int switch_value(int id) {
+  switch_entry& e = switch_table()[id];
+  const int o = e.ovr.load(std::memory_order_relaxed);
+  if (o >= 0) return o;
+  int v = e.env.load(std::memory_order_relaxed);
+  if (v == INT_MIN) {
+    const char* s = getenv(e.name);
+    v = s ? atoi(s) : e.dflt;
+    e.env.store(v, std::memory_order_relaxed);
+  }
+  return v;
+}
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));

@@ -726,6 +726,24 @@ extern "C" int ldmk_init(int device) {
 }
 extern "C" const char* ldmk_last_error(void) { return g_err; }
 
+// test and A/B hooks over the switch table of ldmk_common.h
+static int switch_find(const char* name) {
+  for (int i = 0; name && i < ldmk::SW_COUNT; ++i)
+    if (!strcmp(name, ldmk::switch_table()[i].name)) return i;
+  return -1;
+}
+extern "C" int ldmk_switch_value(const char* name) {
+  const int i = switch_find(name);
+  return i < 0 ? -1 : ldmk::switch_value(i);
+}
+extern "C" int ldmk_switch_override(const char* name, int value) {
+  const int i = switch_find(name);
+  if (i < 0) return -1;
+  const int before = ldmk::switch_value(i);
+  ldmk::switch_table()[i].ovr.store(value < 0 ? -1 : value, std::memory_order_relaxed);
+  return before;
+}
+
 extern "C" int ldmk_dense_small(const float* x, int ldx, const float* w, const float* bias, float* out, int ldo,
                                 int rows, int K, int N, int silu_in, void* stream) {
   LDMK_ENTER();

@@ -452,7 +452,7 @@ static int launch_wgrad_t(const ldmk_wgrad_args& a, int splitr, hipStream_t st) 
   constexpr int BM = 32 * TM * WM, BN = 32 * TN * WN;
   const int tiles = ((a.Kw + BM - 1) / BM) * ((a.N + BN - 1) / BN);
   const int nb = a.batch > 1 ? a.batch : 1;
-  static const bool tr = [] { const char* e = getenv("LDMK_WGRAD_TR"); return !e || atoi(e) != 0; }();      // (=0: the round-2 gather, A/B only)
+  const bool tr = switch_value(SW_WGRAD_TR) != 0;      // (=0: the round-2 gather, A/B only)
   if (BF && tr)
     hipLaunchKernelGGL((wgrad_tr_kernel<TM, TN, WM, WN>), dim3(tiles, splitr, nb), dim3(256), 0, st, a, splitr, a.ws);
   else

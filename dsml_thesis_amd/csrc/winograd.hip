@@ -462,8 +462,7 @@ extern "C" long long ldmk_ps_bytes_h2(int rows, int k);
 
 // LDMK_WINO_STAGED (A/B): 0 routes the public Winograd transforms to the v1 kernels everywhere; same bits.
 static int wino_staged_env() {
-  static const int v = [] { const char* e = getenv("LDMK_WINO_STAGED"); return e ? atoi(e) : 1; }();
-  return v;
+  return ldmk::switch_value(ldmk::SW_WINO_STAGED);
 }
 
 // The patch geometry of the staged input transform (wino_input_ps_staged_kernel), false where a 32-tile block is not whole

@@ -72,6 +72,8 @@ _SIGS = {
     "ldmk_version": (C.c_int, []),
     "ldmk_last_error": (C.c_char_p, []),
     "ldmk_init": (C.c_int, [C.c_int]),
+    "ldmk_switch_value": (C.c_int, [C.c_char_p]),
+    "ldmk_switch_override": (C.c_int, [C.c_char_p, C.c_int]),
     "ldmk_igemm": (C.c_int, [C.POINTER(IgemmArgs), _fp]),
     "ldmk_igemm_workspace_elems": (C.c_longlong, [C.POINTER(IgemmArgs)]),
     "ldmk_igemm_check": (C.c_int, [C.POINTER(IgemmArgs)]),

@@ -36,6 +36,16 @@ const char* ldmk_last_error(void);
  * Returns LDMK_EHIP when there is no such device / it is not gfx950. */
 int ldmk_init(int device);
 
+/* Test and A/B hooks over the library's own switches (LDMK_IG_NFAST, LDMK_IG_LEAN, LDMK_PS_NFAST, LDMK_PS_LEAN, LDMK_ATTN_QB,
+ * LDMK_ATTN_XCD, LDMK_ATTN_PIPE, LDMK_WGRAD_TR, LDMK_WINO_STAGED).  Each is read from the environment once, at the first
+ * launch that consults it; an override stands in front of that value until it is taken back.  Set them BETWEEN launches
+ * only (a launcher reads its switches on the host; work already enqueued is not affected), never from production code.
+ *   ldmk_switch_value:    the effective value; -1: unknown name.
+ *   ldmk_switch_override: value >= 0 overrides, value < 0 returns to the environment / default; the result is the effective
+ *                         value before the call, -1: unknown name. */
+int ldmk_switch_value(const char* name);
+int ldmk_switch_override(const char* name, int value);
+
 /* ------------------------------------------------------------------------------------------
  * Implicit GEMM on the f32 matrix cores (v_mfma_f32_32x32x2_f32):
  *     out[M][N] = epilogue( transform(A)[M][K] * W[K][N] )

@@ -57,17 +57,8 @@ def test_f16x2_attention_peaked_and_flat_rows(ops):
         _f16x2_class(_err(y32, ref), _err(yh, ref), 2e-6)
 
 
-@pytest.mark.parametrize("order", ["rising", "falling", "steps", "peaked", "overflow"])
-@pytest.mark.parametrize("tokens", [2048, 4096])
-def test_f16x2_attention_lazy_running_maximum(ops, tokens, order):
-    """The pipelined key loop (tokens % 256 == 0, two query blocks per wave) takes each 32-key block's probabilities against the
-    maximum the row already has and raises it only when the block's row sum says so (csrc/attention_bf16.hip, h2p_step_lazy).
-    Scores that RISE with the key index cross that bound over and over -- by a little per block, by whole binary orders at a step
-    -- and scores that fall never do; one-hot rows (4 x random: score gaps of tens of binary orders) leave every other probability
-    at the bottom of fp16's range.  Same bar as the exact-maximum kernel: the accuracy class of the fp32 kernel against float64.
-    "overflow" (12 x random: a key 120 binary orders above everything the row has seen overflows the fp32 exponential): outside the
-    kernel's range -- the range flag goes up and the result stays finite, like an operand outside fp16's range."""
-    n, heads = 1, 2
+def lazy_maximum_scores(tokens, order, n=1, heads=2):
+    """[q | k | v] rows whose scores follow one of the orders of test_f16x2_attention_lazy_running_maximum (on the GPU)."""
     C_ = heads * 32
     g = torch.Generator().manual_seed(560)
     q = torch.randn(n * tokens, C_, generator=g)
@@ -83,7 +74,21 @@ def test_f16x2_attention_lazy_running_maximum(ops, tokens, order):
         qdir = torch.nn.functional.normalize(q.reshape(tokens, heads, 32).mean(0), dim=-1)          # (heads, 32)
         q = 0.3 * q + qdir.reshape(1, C_)                                                            # all queries lean the same way
         k = 0.3 * torch.randn(n * tokens, C_, generator=g) + (ramp[:, None] * 60.0 * 32 ** 0.5) * qdir.reshape(1, C_)
-    qkv = torch.cat([q, k, v], dim=1).cuda()
+    return torch.cat([q, k, v], dim=1).cuda()
+
+
+@pytest.mark.parametrize("order", ["rising", "falling", "steps", "peaked", "overflow"])
+@pytest.mark.parametrize("tokens", [2048, 4096])
+def test_f16x2_attention_lazy_running_maximum(ops, tokens, order):
+    """The pipelined key loop (tokens % 256 == 0, two query blocks per wave) takes each 32-key block's probabilities against the
+    maximum the row already has and raises it only when the block's row sum says so (csrc/attention_bf16.hip, h2p_step_lazy).
+    Scores that RISE with the key index cross that bound over and over -- by a little per block, by whole binary orders at a step
+    -- and scores that fall never do; one-hot rows (4 x random: score gaps of tens of binary orders) leave every other probability
+    at the bottom of fp16's range.  Same bar as the exact-maximum kernel: the accuracy class of the fp32 kernel against float64.
+    "overflow" (12 x random: a key 120 binary orders above everything the row has seen overflows the fp32 exponential): outside the
+    kernel's range -- the range flag goes up and the result stays finite, like an operand outside fp16's range."""
+    n, heads = 1, 2
+    qkv = lazy_maximum_scores(tokens, order, n, heads)
     ref = _attention_ref(qkv, n, tokens, heads)
     flag = torch.zeros(1, device="cuda", dtype=torch.int32)
     y32 = ops.attn_self(qkv, n, tokens, heads)

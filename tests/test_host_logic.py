@@ -372,8 +372,9 @@ def test_posterior_helpers_carry_the_reference_formulas():
 def test_every_environment_switch_is_registered_and_documented():
     """dsml_thesis_amd/switches.py is the one table of `LDMK_*` environment switches: every read in the package goes through
     switches.get (no raw os.environ read of an LDMK_ name is left), with the default the table documents; every getenv in the
-    library's sources and every read in bench.py names a registered switch; the table names nothing that is no longer read; and
-    docs/SWITCHES.md is the table's own rendering."""
+    library's sources and every read in bench.py names a registered switch -- the library's own switches through its one table
+    (csrc/ldmk_common.h), with the defaults documented here; the table names nothing that is no longer read; every entry states
+    its contract ("bits", "tolerance" or None); and docs/SWITCHES.md is the table's own rendering."""
     import glob
     import os
     import re
@@ -401,6 +402,20 @@ def test_every_environment_switch_is_registered_and_documented():
             for name in re.findall(r'getenv\("(LDMK_[A-Z0-9_]+)"\)', open(path).read()):
                 assert name in S.PROBE_ONLY or S.SWITCHES.get(name, (None, None))[1] == "library", (name, path)
                 seen.add(name)
+    # the library's own switches: ONE table ({"LDMK_X", default, ...} in csrc/ldmk_common.h, read by getenv(e.name)), with the table's
+    # defaults (unset = 0 there); no other source reads a library switch by itself
+    common = open(os.path.join(root, "dsml_thesis_amd", "csrc", "ldmk_common.h")).read()
+    assert "getenv(e.name)" in common
+    lib_table = dict(re.findall(r'\{"(LDMK_[A-Z0-9_]+)",\s*(-?\d+),', common))
+    assert set(lib_table) == {n for n, v in S.SWITCHES.items() if v[1] == "library"}, sorted(lib_table)
+    for name, default in lib_table.items():
+        assert int(default) == int(S.SWITCHES[name][0] or 0), (name, default)
+        assert name not in seen, f"{name} is read outside the library's switch table"
+        seen.add(name)
+    for name, entry in S.SWITCHES.items():
+        assert len(entry) == 4 and entry[3] in ("bits", "tolerance", None), (name, entry)
+        assert entry[3] is None or entry[1] in ("arithmetic", "route", "library"), (name, entry)
+        assert entry[1] != "library" or entry[3] is not None, f"{name}: a library switch is an A/B arm and states its contract"
     for name in re.findall(r'os\.environ\.get\("(LDMK_[A-Z0-9_]+)"', open(os.path.join(root, "bench.py")).read()):
         assert name in S.SWITCHES, (name, "bench.py")
         seen.add(name)

@@ -456,17 +456,18 @@ def _linear_pinned(ops, x, wp, bias, splitk, **kw):
     return out
 
 
-@pytest.mark.parametrize("case", [
+WINOGRAD_CASES = [
     # n, h, w, c0, c1, cout, GroupNorm+SiLU prologue, epilogue options
     (2, 16, 16, 64, 0, 96, True, "bias+vec+res+stats"),
     (1, 8, 8, 32, 32, 64, True, "bias+stats"),                 # channel concat; W = 8: two tile rows per GroupNorm chunk
     (3, 4, 32, 32, 0, 32, False, "bias+res"),                   # non-square, no prologue
     (1, 64, 64, 32, 0, 32, True, "bias+stats"),                 # W = 64: two chunks per image row
     (1, 4, 128, 32, 0, 32, True, "bias+stats"),                 # W = 128: eight chunks per band
-])
-def test_conv3x3_winograd_matches_conv2d(ops, case):
-    """Winograd F(2x2,3x3) (csrc/winograd.hip + batched igemm) against F.conv2d in float64: openaimodel.py:201-204 / :226-230
-    (GroupNorm -> SiLU -> Conv2d 3x3, + timestep vector, + skip).  Same tolerance as the direct implicit-GEMM convolution."""
+]
+
+
+def winograd_case(ops, case):
+    """One case of WINOGRAD_CASES through ops.conv3x3_winograd: (result, its GroupNorm records or None, float64 reference)."""
     n, h, w, c0, c1, cout, pro, epi = case
     C_ = c0 + c1
     x = rnd(110, n, C_, h, w) * 1.3 + 0.2
@@ -491,6 +492,15 @@ def test_conv3x3_winograd_matches_conv2d(ops, case):
         kw.update(coef=ops.gn_coef(x0, x1, n, h * w, gamma.cuda(), beta.cuda(), 1e-5, groups=32 if C_ % 32 == 0 else 8))
     part = torch.zeros(n * h * w // 32, cout, 3, device="cuda") if "stats" in epi else None
     y = ops.conv3x3_winograd(x0, ops.pack_winograd(wt.cuda()), x1=x1, stats_out=part, **kw)
+    return y, part, ref
+
+
+@pytest.mark.parametrize("case", WINOGRAD_CASES)
+def test_conv3x3_winograd_matches_conv2d(ops, case):
+    """Winograd F(2x2,3x3) (csrc/winograd.hip + batched igemm) against F.conv2d in float64: openaimodel.py:201-204 / :226-230
+    (GroupNorm -> SiLU -> Conv2d 3x3, + timestep vector, + skip).  Same tolerance as the direct implicit-GEMM convolution."""
+    n, h, w, c0, c1, cout, pro, epi = case
+    y, part, ref = winograd_case(ops, case)
     close(nchw(y), ref.float(), 1e-4, 1e-4)
     if part is not None:      # the GroupNorm partial records of the result equal the stand-alone statistics pass
         from dsml_thesis_amd import lib as L
