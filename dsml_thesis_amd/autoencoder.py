@@ -5,7 +5,8 @@ Decoder, model.py:462-568) and `encode` (Encoder -> quant_conv, model.py:368-459
 `AutoencoderKL` (autoencoder.py:285-342): `encode` -> DiagonalGaussianDistribution over the moments the encoder's
 double-width head produces (one kernel, ldmk_conv3x3_moments), `decode` = post_quant_conv -> Decoder.
 `IdentityFirstStage` (autoencoder.py:426-443): pixels are the latents.
-Training-side members of the reference classes (loss, optimisers, EMA of the autoencoder) are out of scope.
+`VQModel`: the trainable sibling of `VQModelInterface` (training_step, optimisers, EMA; train_first_stage.py).
+Training-side members of `AutoencoderKL` are out of scope.
 
 Parameter trees and state-dict keys equal the reference's (`encoder.*`, `decoder.*`, `quant_conv.*`,
 `post_quant_conv.*`, and `quantize.embedding.weight` for the VQ model).  Forward passes are launch programs over
@@ -13,6 +14,7 @@ libldmk.so kernels (NHWC inside, NCHW at the boundary); no PyTorch fallback.  Wh
 weight packing, the block emitters, the decoder program, the encoder trunk and the program cache -- is `_FirstStage`.
 """
 import math
+from contextlib import contextmanager
 
 import torch
 import torch.nn as nn
@@ -388,7 +390,8 @@ class _FirstStage(nn.Module):
         return pg
 
 
-class VQModelInterface(_FirstStage):
+class _VQFirstStage(_FirstStage):
+    """What VQModelInterface and VQModel share: the module tree, the encode program and the two program runners."""
     SKIP_INIT = ("quantize.embedding.weight",)
 
     def __init__(self, embed_dim, ddconfig=None, lossconfig=None, n_embed=None, ckpt_path=None, ignore_keys=[],
@@ -419,11 +422,11 @@ class VQModelInterface(_FirstStage):
         pg.outputs = dict(z=z)
         return pg
 
-    # ---- public surface (autoencoder.py:269-282) ------------------------------------------------------------
     @torch.no_grad()
-    def encode(self, x):
+    def _run_encode(self, x):
+        """Encoder -> quant_conv: the latent before quantisation."""
         if not x.is_cuda:
-            raise L.LdmkError("VQModelInterface.encode: CUDA tensors only (no CPU fallback)")
+            raise L.LdmkError(f"{type(self).__name__}.encode: CUDA tensors only (no CPU fallback)")
         n, _, H, W_ = x.shape
         pg = self._program("enc", n, H, W_)
         pg.inputs["x"].copy_(x)
@@ -431,18 +434,248 @@ class VQModelInterface(_FirstStage):
         return pg.outputs["z"].clone()
 
     @torch.no_grad()
-    def decode(self, h, force_not_quantize=False, return_indices=False):
+    def _run_decode(self, h, quantize, return_indices=False):
+        """(VQ lookup ->) post_quant_conv -> Decoder."""
         if not h.is_cuda:
-            raise L.LdmkError("VQModelInterface.decode: CUDA tensors only (no CPU fallback)")
+            raise L.LdmkError(f"{type(self).__name__}.decode: CUDA tensors only (no CPU fallback)")
         n, _, hh, ww = h.shape
-        pg = self._program("dec", n, hh, ww, not force_not_quantize)
+        pg = self._program("dec", n, hh, ww, quantize)
         pg.inputs["z"].copy_(h)
         pg.run()
         img = pg.outputs["image"].clone()
         return (img, pg.outputs["indices"].clone()) if return_indices else img
 
+
+class VQModelInterface(_VQFirstStage):
+    # ---- public surface (autoencoder.py:269-282) ------------------------------------------------------------
+    def encode(self, x):
+        return self._run_encode(x)
+
+    def decode(self, h, force_not_quantize=False, return_indices=False):
+        return self._run_decode(h, not force_not_quantize, return_indices)
+
     def forward(self, x):
         return self.decode(self.encode(x))
+
+
+class _AdamOfTrainer:
+    """What configure_optimizers hands out for the autoencoder: the step is ldmk_adamw over the trainer's arena."""
+
+    def __init__(self, model, lr, betas=(0.5, 0.9)):
+        self.model, self.betas = model, betas
+        self.param_groups = [dict(lr=lr, betas=betas)]
+
+    def step(self):
+        self.model.trainer().adam_step(self.param_groups[0]["lr"], betas=self.betas)
+        self.model._dirty = True
+
+    def zero_grad(self, set_to_none=False):
+        self.model.trainer().P.grad.zero_()
+
+
+class VQModel(_VQFirstStage):
+    """ldm.models.autoencoder.VQModel (autoencoder.py:14-262) and taming.models.vqgan.VQModel as a trainable drop-in, without
+    Lightning: `training_step(batch, batch_idx, optimizer_idx)` runs the whole autoencoder step on the HIP kernels
+    (train_first_stage.FirstStageTrainer) and returns the loss; `configure_optimizers()` hands out the two optimizers, and
+    `train_batch(batch)` is the loop body Lightning would run (autoencoder step, discriminator step, EMA).  The trained
+    weights live in the trainer's arena and are written back into the nn.Parameters whenever an inference method, the state
+    dict or the EMA scope needs them.  The loss module is not a registered submodule (the first-stage machinery walks
+    `parameters()`); `state_dict()` / `load_state_dict()` carry it under the reference's `loss.` prefix all the same.
+    With use_ema the shadow is a flat copy of the arena (not part of the state dict)."""
+
+    def __init__(self, ddconfig, lossconfig, n_embed, embed_dim, ckpt_path=None, ignore_keys=[], image_key="image",
+                 colorize_nlabels=None, monitor=None, batch_resize_range=None, scheduler_config=None, lr_g_factor=1.0,
+                 remap=None, sane_index_shape=False, use_ema=False):
+        for name, v in (("batch_resize_range", batch_resize_range), ("remap", remap), ("colorize_nlabels", colorize_nlabels),
+                        ("scheduler_config", scheduler_config)):
+            if v is not None:
+                raise NotImplementedError(f"VQModel: {name} is not built")
+        super().__init__(embed_dim, ddconfig=ddconfig, n_embed=n_embed, image_key=image_key, monitor=monitor,
+                         sane_index_shape=sane_index_shape)
+        from .util import instantiate_from_config
+        loss = lossconfig if isinstance(lossconfig, nn.Module) else instantiate_from_config(lossconfig)
+        object.__setattr__(self, "_loss", loss)            # kept out of the module tree (see the class docstring)
+        self.lr_g_factor, self.use_ema = lr_g_factor, use_ema
+        self.learning_rate, self.global_step = 4.5e-6, 0
+        self.logged = {}
+        self._tr, self._dirty, self._shadow, self._ema_updates, self._opts = None, False, None, 0, None
+        if ckpt_path is not None:
+            self.init_from_ckpt(ckpt_path, ignore_keys=ignore_keys)
+
+    # ---- plumbing -----------------------------------------------------------------------------------------------
+    @property
+    def loss(self):
+        return self._loss
+
+    def _apply(self, fn, *a, **kw):
+        if isinstance(self._loss, nn.Module):
+            self._loss._apply(fn)
+        return super()._apply(fn, *a, **kw)
+
+    def trainer(self):
+        if self._tr is None:
+            from .train_first_stage import FirstStageTrainer
+            self._tr = FirstStageTrainer(self)
+            if self.use_ema:
+                self._shadow = self._tr.P.flat.clone()
+        return self._tr
+
+    def _ensure(self):
+        if self._dirty:                          # the arena is ahead of the nn.Parameters
+            self._dirty = False
+            self._tr.sync_to_module()
+        super()._ensure()
+
+    def state_dict(self, *args, destination=None, prefix="", keep_vars=False):
+        """nn.Module.state_dict with the loss module's entries under `<prefix>loss.`, top level or nested in a parent."""
+        if args:                                 # the legacy positional form (destination, prefix, keep_vars)
+            destination, prefix, keep_vars = (list(args) + [prefix, keep_vars][len(args) - 1:])[:3]
+        if self._dirty:
+            self._ensure()
+        sd = super().state_dict(destination=destination, prefix=prefix, keep_vars=keep_vars)
+        if isinstance(self._loss, nn.Module):
+            self._loss.state_dict(destination=sd, prefix=prefix + "loss.", keep_vars=keep_vars)
+        return sd
+
+    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
+        """The hook both `load_state_dict` and a parent module's load go through: the `<prefix>loss.` entries go to the loss
+        module (which is no registered child), and the arena restarts from the loaded weights."""
+        super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs)
+        lp = prefix + "loss."
+        unexpected_keys[:] = [k for k in unexpected_keys if not k.startswith(lp)]
+        mine = {k[len(lp):]: v for k, v in state_dict.items() if k.startswith(lp)}
+        if isinstance(self._loss, nn.Module) and (mine or strict):
+            res = self._loss.load_state_dict(mine, strict=False)
+            missing_keys.extend(lp + k for k in res.missing_keys)
+            unexpected_keys.extend(lp + k for k in res.unexpected_keys)
+        self._tr, self._dirty, self._shadow, self._opts = None, False, None, None
+
+    def log_dict(self, d, **kw):
+        self.logged.update({k: (v.detach() if torch.is_tensor(v) else v) for k, v in d.items()})
+
+    def log(self, k, v, **kw):
+        self.log_dict({k: v})
+
+    # ---- the reference's surface -----------------------------------------------------------------------------------
+    def encode(self, x):
+        from . import train_ops as T
+        h = self._run_encode(x)
+        quant, idx = ops.vq_nearest(h, self.quantize.embedding.weight.detach())
+        emb_loss, _ = T.vq_loss_bwd(h, self.quantize.embedding.weight.detach(), idx.reshape(-1), beta=self.quantize.beta,
+                                    want_dz=False)
+        ind = idx.long().reshape(x.shape[0], h.shape[2], h.shape[3]) if self.quantize.sane_index_shape else idx.long().reshape(-1)
+        return quant, emb_loss, (None, None, ind)
+
+    def encode_to_prequant(self, x):
+        return self._run_encode(x)
+
+    def decode(self, quant):
+        return self._run_decode(quant, False)
+
+    def decode_code(self, code_b):
+        b, h, w = code_b.shape
+        return self.decode(self.quantize.get_codebook_entry(code_b, (b, h, w, self.embed_dim)))
+
+    def forward(self, input, return_pred_indices=False):
+        quant, diff, (_, _, ind) = self.encode(input)
+        dec = self.decode(quant)
+        return (dec, diff, ind) if return_pred_indices else (dec, diff)
+
+    def get_input(self, batch, k):
+        x = batch[k]
+        if len(x.shape) == 3:
+            x = x[..., None]
+        return x.permute(0, 3, 1, 2).to(memory_format=torch.contiguous_format).float()
+
+    def get_last_layer(self):
+        return self.decoder.conv_out.weight
+
+    def training_step(self, batch, batch_idx, optimizer_idx):
+        """optimizer_idx 0: forward, loss, ONE backward through the autoencoder (gradients in trainer().P.grad), -> aeloss.
+        optimizer_idx 1: forward again (the autoencoder may have stepped, as under Lightning), -> the discriminator loss with
+        autograd attached to the discriminator."""
+        from .losses import perplexity_from_counts
+        x = self.get_input(batch, self.image_key).to(next(self.parameters()).device)
+        tr, loss = self.trainer(), self.loss
+        loss.discriminator.train()
+        xrec = tr.forward(x)
+        if optimizer_idx == 0:
+            aeloss, log = loss(tr.qloss, x, xrec, 0, self.global_step, last_layer=tr.last_layer_grad, split="train")
+            tr.backward(loss.d_image, codebook_weight=loss.codebook_weight)
+            log["train/perplexity"], log["train/cluster_usage"] = perplexity_from_counts(tr.counts)
+            self.log_dict(log)
+            return aeloss
+        tr.tape = []
+        discloss, log = loss(tr.qloss, x, xrec, 1, self.global_step, split="train")
+        self.log_dict(log)
+        return discloss
+
+    def configure_optimizers(self):
+        lr_d, lr_g = self.learning_rate, self.lr_g_factor * self.learning_rate
+        self._opts = [_AdamOfTrainer(self, lr_g), torch.optim.Adam(self.loss.discriminator.parameters(), lr=lr_d, betas=(0.5, 0.9))]
+        return self._opts, []
+
+    def train_batch(self, batch, batch_idx=0):
+        """One iteration of the two-optimizer loop: -> (aeloss, discloss)."""
+        opt_ae, opt_disc = self._opts if self._opts is not None else self.configure_optimizers()[0]
+        aeloss = self.training_step(batch, batch_idx, 0)
+        opt_ae.step()
+        opt_disc.zero_grad(set_to_none=True)
+        with torch.enable_grad():
+            discloss = self.training_step(batch, batch_idx, 1)
+            discloss.backward()
+        opt_disc.step()
+        self.on_train_batch_end()
+        self.global_step += 1
+        return aeloss, discloss.detach()
+
+    def on_train_batch_end(self, *args, **kwargs):
+        if self.use_ema:                           # LitEma.forward, ema.py:25-44: decay warms up with the update count
+            self._ema_updates += 1
+            decay = min(0.9999, (1 + self._ema_updates) / (10 + self._ema_updates))
+            self.trainer().ema_update(self._shadow, decay)
+
+    @contextmanager
+    def ema_scope(self, context=None):
+        if self.use_ema:
+            self.trainer().sync_to_module(self._shadow)
+            self._dirty = False
+        try:
+            yield None
+        finally:
+            if self.use_ema:
+                self._tr.sync_to_module()
+
+    @torch.no_grad()
+    def _validation_step(self, batch, batch_idx, suffix=""):
+        x = self.get_input(batch, self.image_key).to(next(self.parameters()).device)
+        xrec, qloss, ind = self(x, return_pred_indices=True)
+        self.loss.discriminator.eval()
+        aeloss, log_ae = self.loss(qloss, x, xrec, 0, self.global_step, last_layer=None, split="val" + suffix, predicted_indices=ind)
+        _, log_disc = self.loss(qloss, x, xrec, 1, self.global_step, split="val" + suffix)
+        log_ae[f"val{suffix}/aeloss"] = aeloss
+        self.log_dict(log_ae)
+        self.log_dict(log_disc)
+        return dict(log_ae, **log_disc)
+
+    def validation_step(self, batch, batch_idx):
+        log = self._validation_step(batch, batch_idx)
+        if self.use_ema:
+            with self.ema_scope():
+                log.update(self._validation_step(batch, batch_idx, suffix="_ema"))
+        return log
+
+    @torch.no_grad()
+    def log_images(self, batch, only_inputs=False, plot_ema=False, **kwargs):
+        x = self.get_input(batch, self.image_key).to(next(self.parameters()).device)
+        log = dict(inputs=x)
+        if only_inputs:
+            return log
+        log["reconstructions"] = self(x)[0]
+        if plot_ema:
+            with self.ema_scope():
+                log["reconstructions_ema"] = self(x)[0]
+        return log
 
 
 class AutoencoderKL(_FirstStage):

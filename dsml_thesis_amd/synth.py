@@ -35,6 +35,10 @@ KL_F4 = dict(embed_dim=3, ddconfig=dict(VQ_F4["ddconfig"], double_z=True))
 KL_F8_SMALL = dict(embed_dim=4,
                    ddconfig=dict(double_z=True, z_channels=4, resolution=64, in_channels=3, out_ch=3, ch=32, ch_mult=[1, 2, 2, 4],
                                  num_res_blocks=1, attn_resolutions=[], dropout=0.0))
+# first-stage training tests: a two-level VQGAN with attention at the latent resolution, 64 codes (2.80 M parameters)
+VQ_TRAIN_SMALL = dict(embed_dim=3, n_embed=64,
+                      ddconfig=dict(double_z=False, z_channels=3, resolution=32, in_channels=3, out_ch=3, ch=64, ch_mult=[1, 2],
+                                    num_res_blocks=1, attn_resolutions=[16], dropout=0.0))
 SCHEDULE = dict(timesteps=1000, linear_start=0.0015, linear_end=0.0205)
 
 
@@ -125,6 +129,16 @@ def make_kl_model(gain=1.0, scale_factor=0.18215, unet=None, kl=None, scale_by_s
     load_recipe(m.model.diffusion_model, gain=gain)
     load_recipe(m.first_stage_model)
     load_recipe(m.cond_stage_model)
+    return m.to(device).eval()
+
+
+def make_vq_first_stage(vq=None, seed=0, device="cuda"):
+    """A stand-alone VQ first stage with recipe weights (what train_first_stage.FirstStageTrainer wraps)."""
+    from .autoencoder import VQModelInterface
+    vq = vq or VQ_TRAIN_SMALL
+    m = VQModelInterface(embed_dim=vq["embed_dim"], n_embed=vq["n_embed"], ddconfig=dict(vq["ddconfig"]),
+                         lossconfig=dict(target="torch.nn.Identity"))
+    load_recipe(m, seed=seed)
     return m.to(device).eval()
 
 

@@ -118,16 +118,21 @@ def pack_dgrad3x3(wp, cin, cout, out=None):
     return out
 
 
-def conv3x3_dgrad(dy, wd, in_hw, stride=1, out=None, residual=None):
-    """Data gradient of a pad-1 3x3 convolution: dy (n,oh,ow,cout), wd = pack_dgrad3x3 weights [9*cout][cin] ->
-    (n,h,w,cin).  stride 2 reads dy zero-inserted (ldmk_igemm upsample=2)."""
+def conv3x3_dgrad(dy, wd, in_hw, stride=1, out=None, residual=None, pad_lo=1):
+    """Data gradient of a 3x3 convolution: dy (n,oh,ow,cout), wd = pack_dgrad3x3 weights [9*cout][cin] ->
+    (n,h,w,cin).  stride 2 reads dy zero-inserted (ldmk_igemm upsample=2).  pad_lo is the FORWARD convolution's: 1 is the
+    pad-1 form; 0 with stride 2 is the encoder's Downsample, F.pad(x, (0,1,0,1)) then a pad-0 convolution (model.py:72-76).
+    With the taps mirrored, input pixel i reads the zero-inserted dy at i - (2 - pad_lo) + tap, so the transposed
+    convolution's own pad_lo is 2 - pad_lo."""
     n, oh, ow, cout = dy.shape
     h, w_ = in_hw
     cin = wd.shape[1]
+    if pad_lo not in (0, 1) or (pad_lo == 0 and stride != 2):
+        raise ValueError(f"conv3x3_dgrad: pad_lo={pad_lo}, stride={stride}: pad_lo is 1, or 0 with stride 2")
     if out is None:
         out = _f32(n, h, w_, cin, device=dy.device)
     a = ops.make_igemm_args(n * h * w_, cin, 9 * cout, dy, cout, wd, out, cin, h * w_, compute=COMPUTE,
-                            conv=(oh, ow, h, w_, 1, 1, 2 if stride == 2 else 0), residual=residual)
+                            conv=(oh, ow, h, w_, 1, 2 - pad_lo, 2 if stride == 2 else 0), residual=residual)
     ops.igemm(a)
     return out
 
@@ -291,6 +296,76 @@ def mse_grad(pred, target, dpred=None, loss=None, denom=0):
     scratch = torch.empty(256, device=pred.device, dtype=torch.float64)
     L.call("ldmk_mse_grad", _ptr(pred), _ptr(target), _ptr(dpred), pred.numel(), denom, _ptr(loss), _ptr(scratch), stream())
     return loss, dpred
+
+
+def l1_grad(pred, target, dpred=None, loss=None, denom=0):
+    """loss = mean|pred - target|, dpred = sign(pred - target) / denom (sign(0) = 0); the sibling of mse_grad."""
+    ops._chk(pred, "l1_grad pred")
+    ops._chk(target, "l1_grad target")
+    if target.numel() != pred.numel():
+        raise ValueError(f"l1_grad: pred {tuple(pred.shape)} against target {tuple(target.shape)}")
+    dpred = torch.empty_like(pred) if dpred is None else dpred
+    loss = _f32(1, device=pred.device) if loss is None else loss
+    scratch = torch.empty(256, device=pred.device, dtype=torch.float64)
+    L.call("ldmk_l1_grad", _ptr(pred), _ptr(target), _ptr(dpred), pred.numel(), denom, _ptr(loss), _ptr(scratch), stream())
+    return loss, dpred
+
+
+def _vq_dims(z, codebook, idx):
+    ops._chk(z, "vq z")
+    ops._chk(codebook, "vq codebook")
+    n, dim, h, w_ = z.shape
+    if not (idx.is_cuda and idx.is_contiguous()) or codebook.shape[1] != dim or idx.dtype != torch.int32 or idx.numel() != n * h * w_:
+        raise ValueError(f"vq: z {tuple(z.shape)}, codebook {tuple(codebook.shape)}, idx {idx.dtype} x {idx.numel()} "
+                         "(int32, one per latent vector, as ops.vq_nearest writes it)")
+    return n, dim, h * w_
+
+
+def vq_loss_bwd(z, codebook, idx, dzq=None, beta=0.25, legacy=True, w=1.0, dz=None, loss=None, want_dz=True):
+    """The codebook loss of VectorQuantizer2 and its gradient w.r.t. the encoder output: z (n,dim,h,w) NCHW, dzq the
+    gradient that arrives at the quantised latent (straight-through).  -> (loss[1], dz); loss is not scaled by w."""
+    n, dim, hw = _vq_dims(z, codebook, idx)
+    for t in (dzq, dz):
+        ops._chk(t, "vq_loss_bwd dzq / dz")
+        if t is not None and t.shape != z.shape:
+            raise ValueError(f"vq_loss_bwd: dzq / dz {tuple(t.shape)} against z {tuple(z.shape)}")
+    if want_dz and dz is None:
+        dz = torch.empty_like(z)
+    loss = _f32(1, device=z.device) if loss is None else loss
+    scratch = torch.empty(256, device=z.device, dtype=torch.float64)
+    L.call("ldmk_vq_loss_bwd", _ptr(z), _ptr(codebook), _ptr(idx), _ptr(dzq), _ptr(dz), _ptr(loss), n, hw, dim,
+           codebook.shape[0], beta, 1 if legacy else 0, w, _ptr(scratch), stream())
+    return loss, dz
+
+
+def vq_codebook_grad(z, codebook, idx, beta=0.25, legacy=True, w=1.0, dE=None, count=None):
+    """-> (dE (n_e,dim), count (n_e,) int32): the codebook's gradient of the codebook loss and the hits per code."""
+    n, dim, hw = _vq_dims(z, codebook, idx)
+    dE = torch.empty_like(codebook) if dE is None else dE
+    count = torch.empty(codebook.shape[0], device=z.device, dtype=torch.int32) if count is None else count
+    L.call("ldmk_vq_codebook_grad", _ptr(z), _ptr(codebook), _ptr(idx), _ptr(dE), _ptr(count), n, hw, dim,
+           codebook.shape[0], beta, 1 if legacy else 0, w, stream())
+    return dE, count
+
+
+def conv1x1_nchw_bwd(x, dy, w, dx=None, dw=None, db=None, accumulate=False, want_dx=True):
+    """Backward of ops.conv1x1_nchw: x (n,cin,h,w), dy (n,cout,h,w), w (cout,cin[,1,1]) -> (dx, dw (cout,cin), db)."""
+    n, cin, h, w_ = x.shape
+    cout = dy.shape[1]
+    for t in (x, dy, w, dx, dw, db):
+        ops._chk(t, "conv1x1_nchw_bwd")
+    if dy.shape != (n, cout, h, w_) or w.numel() != cout * cin or (dx is not None and dx.shape != x.shape):
+        raise ValueError(f"conv1x1_nchw_bwd: x {tuple(x.shape)}, dy {tuple(dy.shape)}, w {tuple(w.shape)}")
+    if want_dx and dx is None:
+        dx = torch.empty_like(x)
+    if accumulate and (dw is None or db is None):
+        raise ValueError("conv1x1_nchw_bwd: accumulate needs dw and db")
+    dw = _f32(cout, cin, device=x.device) if dw is None else dw
+    db = _f32(cout, device=x.device) if db is None else db
+    scratch = torch.empty(9216, device=x.device, dtype=torch.float64)
+    L.call("ldmk_conv1x1_nchw_bwd", _ptr(x), _ptr(dy), _ptr(w), _ptr(dx), _ptr(dw), _ptr(db), n, h * w_, cin, cout,
+           1 if accumulate else 0, _ptr(scratch), stream())
+    return dx, dw, db
 
 
 def adamw_(p, g, m, v, lr, betas, eps, weight_decay, step):

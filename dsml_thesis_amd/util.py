@@ -7,6 +7,11 @@ import importlib
 TARGET_MAP = {
     "ldm.modules.diffusionmodules.openaimodel.UNetModel": "dsml_thesis_amd.unet.UNetModel",
     "ldm.models.autoencoder.VQModelInterface": "dsml_thesis_amd.autoencoder.VQModelInterface",
+    "ldm.models.autoencoder.VQModel": "dsml_thesis_amd.autoencoder.VQModel",
+    "taming.models.vqgan.VQModel": "dsml_thesis_amd.autoencoder.VQModel",
+    "ldm.modules.losses.vqperceptual.VQLPIPSWithDiscriminator": "dsml_thesis_amd.losses.VQLPIPSWithDiscriminator",
+    "ldm.modules.losses.VQLPIPSWithDiscriminator": "dsml_thesis_amd.losses.VQLPIPSWithDiscriminator",
+    "taming.modules.losses.vqperceptual.VQLPIPSWithDiscriminator": "dsml_thesis_amd.losses.VQLPIPSWithDiscriminator",
     "ldm.models.autoencoder.AutoencoderKL": "dsml_thesis_amd.autoencoder.AutoencoderKL",
     "ldm.models.autoencoder.IdentityFirstStage": "dsml_thesis_amd.autoencoder.IdentityFirstStage",
     "ldm.models.diffusion.ddpm.LatentDiffusion": "dsml_thesis_amd.ddpm.LatentDiffusion",

@@ -773,6 +773,30 @@ int ldmk_ddim_diff_fwd(const float* x, int x_channels, const float* eps, const f
 int ldmk_ddim_diff_bwd(const float* dx_prev, const float* dxin, int in_channels, float* dx, float* deps, int cpad, int n, int C,
                        int hw, float cx, float ce, float scale, int guided, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * First-stage (VQGAN) training (csrc/vq_train.hip).  No float atomics: every sum has one fixed order and is bitwise
+ * reproducible; sums are kept in double.
+ * The codebook loss of VectorQuantizer2.forward, taming/modules/vqvae/quantize.py:288-296, for z NCHW [n][dim][hw]
+ * (dim 3 or 4), codebook [n_embed][dim], idx[n*hw] as ldmk_vq_nearest writes it, N = n*hw*dim, m = mean((e_idx - z)^2):
+ *   loss = m + beta*m (unweighted; legacy or not, the reference's two terms have this value)
+ *   dz   = dzq + w c_z (2/N) (z - e_idx)      (dzq NULL: zero; dz NULL: loss only)   scratch = 256 doubles
+ *   dE[j] = w c_e (2/N) sum_{r: idx_r = j} (e_j - z_r), exact zero rows for unused codes; count[j] = hits (NULL: skipped)
+ * with (c_z, c_e) = (1, beta) when legacy != 0 (what the reference constructs) and (beta, 1) otherwise.
+ * An index outside [0, n_embed) is clamped into it. */
+int ldmk_vq_loss_bwd(const float* z, const float* codebook, const int* idx, const float* dzq, float* dz, float* loss, int n,
+                     int hw, int dim, int n_embed, float beta, int legacy, float w, double* scratch, void* stream);
+int ldmk_vq_codebook_grad(const float* z, const float* codebook, const int* idx, float* dE, int* count, int n, int hw, int dim,
+                          int n_embed, float beta, int legacy, float w, void* stream);
+/* Backward of ldmk_conv1x1_nchw, cin, cout <= 8: dx[n][cin][hw] = W^T dy, dw[cout][cin] (+)= sum_{n,hw} dy x,
+ * db[cout] (+)= sum_{n,hw} dy.  Any of dx / dw / db may be NULL (w is needed for dx, x for dw);
+ * scratch = 9216 doubles (dw / db only). */
+int ldmk_conv1x1_nchw_bwd(const float* x, const float* dy, const float* w, float* dx, float* dw, float* db, int n, int hw,
+                          int cin, int cout, int accumulate, double* scratch, void* stream);
+/* loss = mean|pred-target|, dpred = sign(pred-target)/denom with sign(0) = 0 (vqperceptual.py:28-31 'l1'); the arguments
+ * of ldmk_mse_grad */
+int ldmk_l1_grad(const float* pred, const float* target, float* dpred, long long n, long long denom, float* loss,
+                 double* scratch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
