@@ -293,7 +293,7 @@ class _FirstStage(nn.Module):
         zc, ed = d.z_channels, self.embed_dim               # latents carry embed_dim channels, post_quant_conv -> z_channels
         z_in = pg.alloc(n, ed, h, w)
         pg.inputs = dict(z=z_in)
-        idx = pg.alloc(n * h * w, dtype=torch.int32) if hasattr(self, "quantize") else None
+        idx = pg.alloc(n * h * w, dtype=torch.int32) if quantize else None      # (written by ldmk_vq_nearest only: no lookup, no indices)
         zcur = z_in
         if quantize:
             zq = pg.alloc(n, ed, h, w)
@@ -439,6 +439,8 @@ class _VQFirstStage(_FirstStage):
         if not h.is_cuda:
             raise L.LdmkError(f"{type(self).__name__}.decode: CUDA tensors only (no CPU fallback)")
         n, _, hh, ww = h.shape
+        if return_indices and not quantize:
+            raise L.LdmkError(f"{type(self).__name__}.decode: return_indices needs the codebook lookup (force_not_quantize skips it)")
         pg = self._program("dec", n, hh, ww, quantize)
         pg.inputs["z"].copy_(h)
         pg.run()

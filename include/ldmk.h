@@ -118,10 +118,11 @@ typedef struct ldmk_igemm_args {
   int rows_per_sample;       /* rows of A/out per batch item (H*W of the output)                  */
   const float* w;            /* b_trans=0: [K][ldb] row-major (packed) ; 1: [N][ldb] (torch [out][in]) */
   int b_trans, ldb;
-  const float* bias;         /* [N] or NULL                                                       */
-  const float* batch_vec;    /* [n][batch_vec_ld] per-sample vector added to every row, or NULL   */
+  const float* bias;         /* [N] or NULL (batched: the same [N] for every batch entry)         */
+  const float* batch_vec;    /* [n][batch_vec_ld] per-sample vector added to every row, or NULL: N floats are read
+                                from row M / rows_per_sample - 1 at most                          */
   int batch_vec_ld;
-  const float* residual;     /* [M][ldc] or NULL (may alias out)                                  */
+  const float* residual;     /* [M][ldc] or NULL (may alias out); batched: stepped by out_bstride like out */
   int epi;                   /* LDMK_EPI_*; GEGLU: packed (value,gate) 32-column pairs, out has N/2 cols */
   float* out;                /* [M][ldc]                                                          */
   int ldc;
@@ -181,7 +182,8 @@ typedef struct ldmk_igemm_args {
    * ldmk_ps_bytes(R, K) is the size.  The kernel moves these planes memory -> LDS with LDS-DMA loads and does no arithmetic
    * on them: rows mode, a_tf NONE or LAYERNORM_FOLDED, K % 32 == 0, N % 32 == 0.  Same products, product order and split-K
    * partition as tile_cfg 1 / 5: bitwise equal results at equal splitk. */
-  const void* a_ps;          /* A[M][K] in the PS layout (ldmk_pack_ps, ldmk_ln_stats_ps, out_ps of a producer GEMM, ...); a0 is not read */
+  const void* a_ps;          /* A[M][K] in the PS layout (ldmk_pack_ps, ldmk_ln_stats_ps, out_ps of a producer GEMM, ...); a0 is not read.
+                                LDMK_A_CONV3X3 (ldmk_gn_apply_ps_h2 below): the stored activation [n in_h in_w][c0 + c1], not the im2col matrix */
   long long a_ps_bstride;    /*   BYTES between batch entries                                                               */
   const void* w_ps;          /* the weights as X[N][K] (row = output column) in the PS layout: ldmk_pack_ps(w, N, K, 1, ldb)   */
   long long w_ps_bstride;    /*   BYTES between batch entries                                                               */
