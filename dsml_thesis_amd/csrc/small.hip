@@ -426,6 +426,86 @@ __global__ void ddim_advance_kernel(int* step_idx, const long long* __restrict__
   if (threadIdx.x == 0) *step_idx = index;
 }
 
+// ---------------------------------------------------------------------------------------------
+// PLMS update (plms.py:199-236): the DDIM update of ddim_step_kernel (eta = 0) applied to a combination e' of the current
+// and up to three past guidance-combined model outputs.  The past outputs live in a three-slot ring on the device,
+// hist[3][total]; the output of schedule index k sits in slot k % 3, so the ring needs no head pointer: while the index walks
+// down by one per step, the outputs of the previous three steps (indices k+1, k+2, k+3) are in slots (k+1)%3, (k+2)%3, (k+3)%3.
+// The last of these IS the slot e_t goes to.  Three slots suffice because every thread reads hist[(k+3)%3][i] before it writes
+// e_t to that same slot and element i, and no other thread touches element i.
+//   mode 0 multistep: order from the device count (0: e_t itself; 1-3: Adams-Bashforth 2-4), e_t stored
+//   mode 1 Euler predictor: e' = e_t, e_t stored, x copied to x_keep (x_prev may be x itself)
+//   mode 2 Euler corrector: e' = (e_t from the ring + eps) / 2; `x` is the kept latent; the ring keeps e_t
+// The sums are formed in the reference's order with every product and sum rounded on its own (no fused multiply-add), then
+// divided by 2, 12 or 24.
+enum { PLMS_MULTISTEP = 0, PLMS_PREDICTOR = 1, PLMS_CORRECTOR = 2 };
+
+// (x_prev may be x, so neither is __restrict__)
+__global__ void plms_step_kernel(const float* x, const float* __restrict__ eps, const float* __restrict__ table,
+                                 const int* __restrict__ step_idx, const int* __restrict__ count, float cfg_scale, int cfg,
+                                 int mode, float* __restrict__ hist, float* x_keep, float* x_prev,
+                                 float* __restrict__ pred_x0, long long total) {
+  const int index = *step_idx;
+  const int order = mode == PLMS_MULTISTEP ? *count : 0;
+  const float a_t = table[4 * index], a_prev = table[4 * index + 1], s1m = table[4 * index + 3];
+  // same fp32 operation order as the reference expressions (sigma is 0: make_schedule refuses any other eta)
+  const float sqrt_at = sqrtf(a_t);
+  const float dir_c = sqrtf(1.0f - a_prev);
+  const float sqrt_ap = sqrtf(a_prev);
+  float* __restrict__ h0 = hist + (long long)(index % 3) * total;              // e_t's slot == the slot of e_3
+  const float* __restrict__ h1 = hist + (long long)((index + 1) % 3) * total;
+  const float* __restrict__ h2 = hist + (long long)((index + 2) % 3) * total;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+    float e;
+    if (cfg) {
+      const float eu = eps[i], ec = eps[total + i];
+      e = eu + cfg_scale * (ec - eu);
+    } else {
+      e = eps[i];
+    }
+    float ep;
+    if (mode == PLMS_CORRECTOR) {
+      ep = __fadd_rn(h0[i], e) / 2.0f;
+    } else {
+      if (order >= 3) {
+        const float e3 = h0[i];                                                // read BEFORE the store below
+        ep = __fsub_rn(__fadd_rn(__fsub_rn(__fmul_rn(55.0f, e), __fmul_rn(59.0f, h1[i])), __fmul_rn(37.0f, h2[i])),
+                       __fmul_rn(9.0f, e3)) / 24.0f;
+      } else if (order == 2) {
+        ep = __fadd_rn(__fsub_rn(__fmul_rn(23.0f, e), __fmul_rn(16.0f, h1[i])), __fmul_rn(5.0f, h2[i])) / 12.0f;
+      } else if (order == 1) {
+        ep = __fsub_rn(__fmul_rn(3.0f, e), h1[i]) / 2.0f;
+      } else {
+        ep = e;
+      }
+      h0[i] = e;
+    }
+    const float xv = x[i];
+    if (mode == PLMS_PREDICTOR && x_keep) x_keep[i] = xv;
+    const float p0 = (xv - s1m * ep) / sqrt_at;
+    x_prev[i] = sqrt_ap * p0 + dir_c * ep;
+    if (pred_x0) pred_x0[i] = p0;
+  }
+}
+
+// runs after plms_step_kernel on the same stream.  multistep: count = min(count + 1, 3), index one down, ts[:] =
+// timesteps[index]; predictor: ts[:] = timesteps[max(index - 1, 0)] (t_next, plms.py:145), nothing else moves;
+// corrector: count = 1, index one down, ts[:] = timesteps[index]
+__global__ void plms_advance_kernel(int* step_idx, int* count, const long long* __restrict__ timesteps,
+                                    long long* __restrict__ ts, int n_ts, int mode, int n_steps) {
+  int index = *step_idx - 1;
+  if (index < 0) index = 0;
+  if (index > n_steps - 1) index = n_steps - 1;
+  const long long t = timesteps[index];
+  const int c = *count;
+  for (int i = threadIdx.x; i < n_ts; i += blockDim.x) ts[i] = t;
+  __syncthreads();
+  if (threadIdx.x == 0 && mode != PLMS_PREDICTOR) {
+    *step_idx = index;
+    *count = mode == PLMS_CORRECTOR ? 1 : (c < 3 ? c + 1 : 3);
+  }
+}
+
 // ancestral DDPM update (ddpm.py:215-228,1049-1109), per-sample timestep
 __global__ void ddpm_step_kernel(const float* __restrict__ x, const float* __restrict__ eps,
                                  const float* __restrict__ noise, const float* __restrict__ tables,
@@ -868,6 +948,25 @@ extern "C" int ldmk_ddim_step(const float* x, const float* eps, const float* noi
     hipLaunchKernelGGL(ddim_advance_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, step_idx,
                        timesteps, ts, n_ts, advance, n_steps);
   return check_launch("ldmk_ddim_step");
+}
+
+extern "C" int ldmk_plms_step(const float* x, const float* eps, const float* table, int* step_idx, int* count,
+                              float cfg_scale, int cfg, int mode, float* hist, float* x_keep, float* x_prev,
+                              float* pred_x0, long long per_sample, int n, const long long* timesteps, long long* ts,
+                              int n_ts, int advance, int n_steps, void* stream) {
+  LDMK_ENTER();
+  LDMK_REQUIRE(x && eps && table && step_idx && count && hist && x_prev && per_sample > 0 && n > 0, "ldmk_plms_step: bad args");
+  LDMK_REQUIRE(mode == PLMS_MULTISTEP || mode == PLMS_PREDICTOR || mode == PLMS_CORRECTOR,
+               "ldmk_plms_step: mode is 0 (multistep), 1 (Euler predictor) or 2 (Euler corrector)");
+  if (advance) LDMK_REQUIRE(timesteps && ts && n_ts > 0 && n_steps > 0 && advance == 1,
+                            "ldmk_plms_step: advance (+1: the sampler walks down) needs timesteps/ts/n_steps");
+  long long total = per_sample * n;
+  hipLaunchKernelGGL(plms_step_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, x, eps, table, step_idx,
+                     count, cfg_scale, cfg, mode, hist, x_keep, x_prev, pred_x0, total);
+  if (advance)
+    hipLaunchKernelGGL(plms_advance_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, step_idx, count, timesteps, ts, n_ts,
+                       mode, n_steps);
+  return check_launch("ldmk_plms_step");
 }
 
 extern "C" int ldmk_advance_timestep(int* step_idx, const long long* timesteps, long long* ts, int n_ts, int advance,

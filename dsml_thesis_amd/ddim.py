@@ -10,6 +10,8 @@ be captured once in a hipGraph and replayed S times.  Additions over the referen
 per-step noise for eta>0 parity), `use_graph=`, `policy_batch=` (sharding-invariant tile choice) and
 `fixed_identity=` for progressive sampling.
 """
+import types
+
 import numpy as np
 import torch
 
@@ -111,6 +113,65 @@ class DDIMSampler(object):
             return None, cond                    # DiffusionWrapper 'concat': the conditioning is the channel concat (ddpm.py:1407-1409)
         return cond, None
 
+    def _prepare_run(self, cond, shape, x_T, unconditional_guidance_scale, unconditional_conditioning, policy_batch, loops_name):
+        """What every sampling loop of this class does before its first step: start noise, conditioning split, guidance
+        doubling, 'adm' labels, the launch program (or the patch-wise evaluator) with its conditioning written and its context
+        program run, and the per-program dict `loops` that holds loop state under `loops_name` (one name per kind of loop, so the
+        loops never meet each other's state)."""
+        dev = self.model.device
+        unet = self.model.model.diffusion_model
+        b = shape[0]
+        img0 = torch.randn(shape, device=dev) if x_T is None else x_T.to(dev, torch.float32)
+        ctx, cat = self._split_cond(cond)
+        cfg = not (unconditional_conditioning is None or unconditional_guidance_scale == 1.)
+        nb = 2 * b if cfg else b
+        y_in = None
+        if self._is_adm():
+            # class-conditional model (ddpm.py:1417-1419): the conditioning is the label vector y, which reaches the UNet as rows of
+            # its label embedding added to the timestep embedding -- constant over the run, written once into the program's
+            # `y_emb` input; guidance doubles it as [uncond | cond] like any conditioning (ddim.py:175)
+            y_in = ctx if not cfg else torch.cat([self._split_cond(unconditional_conditioning)[0], ctx])
+            assert y_in is not None and y_in.dim() == 1 and cat is None, "conditioning_key 'adm': conditioning = class labels (B,)"
+            ctx_in, cat_in = None, None
+        elif cfg:
+            uc, ucat = self._split_cond(unconditional_conditioning)
+            if ctx is None:                                # 'concat' conditioning: the guidance halves differ in the concat tensor
+                ctx_in, cat_in = None, torch.cat([ucat, cat])
+            else:
+                ctx_in = torch.cat([uc, ctx])              # ddim.py:175: [uncond | cond]
+                cat_in = None if cat is None else torch.cat([cat] * 2)
+        else:
+            ctx_in, cat_in = ctx, cat
+        ncat = 0 if cat_in is None else cat_in.shape[1]
+        L_ctx = 0 if ctx_in is None else ctx_in.shape[1]          # 0: unconditional UNet (no cross-attention)
+        policy_nb = None if policy_batch is None else (2 * policy_batch if cfg else policy_batch)
+        y_emb = None if y_in is None else unet.label_emb.weight.detach().float()[y_in.to(dev, torch.int64)]
+        if hasattr(self.model, "split_input_params"):
+            # patch-wise (ddpm.py:904-986): the latent lives in a full-size buffer of nb items ([uncond | cond] under guidance, so
+            # ldmk_ddim_step's contract holds); one step = unfold -> the program at batch L*nb -> fold -> the update on the
+            # full-size tensors.  Context / concat crops are written once per run.
+            pe = self.model._patched_eval(nb, shape[1], shape[2], shape[3], L_ctx, ncat, policy_batch=policy_nb)
+            pg = pe.pg
+            pe.set_cond(ctx_in, cat_in, y_emb)
+            x_buf, eps, run_net = pe.x, pe.eps, pe.run
+            loops = pe.loops.setdefault(loops_name, {})    # (never the plain loop's state of the same program)
+        else:
+            unet.policy_batch = policy_nb
+            pg = unet.program(nb, shape[2], shape[3], L_ctx, ncat)
+            x_buf, eps, run_net = pg.inputs["x"], pg.outputs["eps"], pg.run
+            if L_ctx:
+                pg.inputs["context"].copy_(ctx_in.reshape(nb * L_ctx, -1))
+            if ncat:
+                pg.inputs["c_concat"].copy_(cat_in)
+            if y_emb is not None:
+                pg.inputs["y_emb"].copy_(y_emb)
+            pg.ctx_program.run()                           # context-only projections: once per sample() call
+            # loop state (buffers, the captured step) lives ON the launch program it was captured over and dies with it: when the
+            # model drops its programs (a re-pack, an arithmetic fall-back) nothing keeps the old workspace or its hipGraph alive,
+            # and a new program can never be handed buffers of another batch size (rounds 2-4 keyed a sampler-side cache by id(pg))
+            loops = pg.__dict__.setdefault(f"_{loops_name}_loops", {})
+        return types.SimpleNamespace(dev=dev, b=b, img0=img0, cfg=cfg, pg=pg, x_buf=x_buf, eps=eps, run_net=run_net, loops=loops)
+
     @torch.no_grad()
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None,
                img_callback=None, quantize_x0=False, eta=0., mask=None, x0=None, temperature=1.,
@@ -156,59 +217,9 @@ class DDIMSampler(object):
           quantize_denoised  pred_x0 snapped to the first stage's codebook before x_prev is formed (:195-196)
           score_corrector    `modify_score(model, e_t, x, t, c, **corrector_kwargs)` between the UNet and the update (:179-181);
                              a host callback, so it runs with eager launches."""
-        dev = self.model.device
-        unet = self.model.model.diffusion_model
-        b = shape[0]
+        r = self._prepare_run(cond, shape, x_T, unconditional_guidance_scale, unconditional_conditioning, policy_batch, "ddim")
+        dev, b, img0, cfg, pg, x_buf, eps, run_net, loops = r.dev, r.b, r.img0, r.cfg, r.pg, r.x_buf, r.eps, r.run_net, r.loops
         S = self.ddim_timesteps.shape[0]
-        img0 = torch.randn(shape, device=dev) if x_T is None else x_T.to(dev, torch.float32)
-        ctx, cat = self._split_cond(cond)
-        cfg = not (unconditional_conditioning is None or unconditional_guidance_scale == 1.)
-        nb = 2 * b if cfg else b
-        y_in = None
-        if self._is_adm():
-            # class-conditional model (ddpm.py:1417-1419): the conditioning is the label vector y, which reaches the UNet as rows of
-            # its label embedding added to the timestep embedding -- constant over the run, written once into the program's
-            # `y_emb` input; guidance doubles it as [uncond | cond] like any conditioning (ddim.py:175)
-            y_in = ctx if not cfg else torch.cat([self._split_cond(unconditional_conditioning)[0], ctx])
-            assert y_in is not None and y_in.dim() == 1 and cat is None, "conditioning_key 'adm': conditioning = class labels (B,)"
-            ctx_in, cat_in = None, None
-        elif cfg:
-            uc, ucat = self._split_cond(unconditional_conditioning)
-            if ctx is None:                                # 'concat' conditioning: the guidance halves differ in the concat tensor
-                ctx_in, cat_in = None, torch.cat([ucat, cat])
-            else:
-                ctx_in = torch.cat([uc, ctx])              # ddim.py:175: [uncond | cond]
-                cat_in = None if cat is None else torch.cat([cat] * 2)
-        else:
-            ctx_in, cat_in = ctx, cat
-        ncat = 0 if cat_in is None else cat_in.shape[1]
-        L_ctx = 0 if ctx_in is None else ctx_in.shape[1]          # 0: unconditional UNet (no cross-attention)
-        policy_nb = None if policy_batch is None else (2 * policy_batch if cfg else policy_batch)
-        y_emb = None if y_in is None else unet.label_emb.weight.detach().float()[y_in.to(dev, torch.int64)]
-        if hasattr(self.model, "split_input_params"):
-            # patch-wise (ddpm.py:904-986): the latent lives in a full-size buffer of nb items ([uncond | cond] under guidance, so
-            # ldmk_ddim_step's contract holds); one step = unfold -> the program at batch L*nb -> fold -> the update on the
-            # full-size tensors.  Context / concat crops are written once per run.
-            pe = self.model._patched_eval(nb, shape[1], shape[2], shape[3], L_ctx, ncat, policy_batch=policy_nb)
-            pg = pe.pg
-            pe.set_cond(ctx_in, cat_in, y_emb)
-            x_buf, eps, run_net = pe.x, pe.eps, pe.run
-            loops = pe.loops.setdefault("ddim", {})        # (never the plain loop's state of the same program)
-        else:
-            unet.policy_batch = policy_nb
-            pg = unet.program(nb, shape[2], shape[3], L_ctx, ncat)
-            x_buf, eps, run_net = pg.inputs["x"], pg.outputs["eps"], pg.run
-            if L_ctx:
-                pg.inputs["context"].copy_(ctx_in.reshape(nb * L_ctx, -1))
-            if ncat:
-                pg.inputs["c_concat"].copy_(cat_in)
-            if y_emb is not None:
-                pg.inputs["y_emb"].copy_(y_emb)
-            pg.ctx_program.run()                           # context-only projections: once per sample() call
-            # loop state (buffers, the captured step) lives ON the launch program it was captured over and dies with it: when the
-            # model drops its programs (a re-pack, an arithmetic fall-back) nothing keeps the old workspace or its hipGraph alive,
-            # and a new program can never be handed buffers of another batch size (rounds 2-4 keyed a sampler-side cache by id(pg))
-            loops = pg.__dict__.setdefault("_ddim_loops", {})
         lib = pg.lib
         n_ts = pg.inputs["t"].numel()                      # (patch-wise: L*nb entries, all the current timestep)
         img = x_buf[:b]                                    # the latent lives in the UNet's input buffer (patch-wise: the full-size one)
@@ -338,15 +349,9 @@ class DDIMSampler(object):
             return out, intermediates["x_inter"]
         return out, intermediates
 
-    @torch.no_grad()
-    def p_sample_ddim(self, x, c, t, index, repeat_noise=False, use_original_steps=False, quantize_denoised=False,
-                      temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None,
-                      unconditional_guidance_scale=1., unconditional_conditioning=None, noise=None):
-        """Single step with the reference's signature (ddim.py:164-203); returns (x_prev, pred_x0).  use_original_steps: `index`
-        counts the model's own timesteps (`_original_tables`)."""
-        dev = x.device
-        b = x.shape[0]
-        table = self._original_tables()[0] if use_original_steps else self._table
+    def _model_output(self, x, c, t, unconditional_guidance_scale, unconditional_conditioning, score_corrector, corrector_kwargs):
+        """One model evaluation of a single-step entry point (ddim.py:170-181, plms.py:178-192) -> (e, cfg).  cfg True: `e` holds
+        2b items [uncond | cond] for the update kernel to combine; False: `e` is the (guidance-combined, corrected) score."""
         ctx, cat = self._split_cond(c)
         cfg = not (unconditional_conditioning is None or unconditional_guidance_scale == 1.)
         if cfg:
@@ -365,6 +370,18 @@ class DDIMSampler(object):
                 e = e_u + unconditional_guidance_scale * (e_c - e_u)
                 cfg = False
             e = score_corrector.modify_score(self.model, e, x, t, c, **(corrector_kwargs or {})).contiguous()
+        return e, cfg
+
+    @torch.no_grad()
+    def p_sample_ddim(self, x, c, t, index, repeat_noise=False, use_original_steps=False, quantize_denoised=False,
+                      temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None,
+                      unconditional_guidance_scale=1., unconditional_conditioning=None, noise=None):
+        """Single step with the reference's signature (ddim.py:164-203); returns (x_prev, pred_x0).  use_original_steps: `index`
+        counts the model's own timesteps (`_original_tables`)."""
+        dev = x.device
+        b = x.shape[0]
+        table = self._original_tables()[0] if use_original_steps else self._table
+        e, cfg = self._model_output(x, c, t, unconditional_guidance_scale, unconditional_conditioning, score_corrector, corrector_kwargs)
         if self._eta != 0.:
             noise = (torch.randn_like(x) if noise is None else noise.to(dev)) * temperature
             if noise_dropout > 0.:

@@ -14,6 +14,7 @@ TF_NONE, TF_AFFINE, TF_AFFINE_SILU, TF_LAYERNORM, TF_LAYERNORM_FOLDED = 0, 1, 2,
 EPI_NONE, EPI_GEGLU = 0, 1
 COMPUTE_F32, COMPUTE_BF16, COMPUTE_BF16X3, COMPUTE_F16X2 = 0, 1, 2, 3
 POST_NONE, POST_GROUPNORM, POST_LAYERNORM = 0, 1, 2
+PLMS_MULTISTEP, PLMS_PREDICTOR, PLMS_CORRECTOR = 0, 1, 2
 
 _fp = C.c_void_p  # device pointers travel as integers (tensor.data_ptr())
 
@@ -142,6 +143,8 @@ _SIGS = {
     "ldmk_conv1x1_nchw": (C.c_int, [_fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
     "ldmk_ddim_step": (C.c_int, [_fp, _fp, _fp, _fp, _fp, C.c_float, C.c_int, _fp, _fp, C.c_longlong, C.c_int, _fp, _fp,
                                  C.c_int, C.c_int, C.c_int, _fp]),
+    "ldmk_plms_step": (C.c_int, [_fp, _fp, _fp, _fp, _fp, C.c_float, C.c_int, C.c_int, _fp, _fp, _fp, _fp, C.c_longlong, C.c_int,
+                                 _fp, _fp, C.c_int, C.c_int, C.c_int, _fp]),
     "ldmk_advance_timestep": (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_int, C.c_int, _fp]),
     "ldmk_ddpm_step": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_longlong, C.c_int, _fp]),
     "ldmk_patch_unfold": (C.c_int, [_fp, _fp] + [C.c_int] * 10 + [_fp]),

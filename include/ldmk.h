@@ -536,6 +536,23 @@ int ldmk_conv1x1_nchw(const float* x, const float* w, const float* bias, float* 
 int ldmk_ddim_step(const float* x, const float* eps, const float* noise, const float* table, int* step_idx,
                    float cfg_scale, int cfg, float* x_prev, float* pred_x0, long long per_sample, int n,
                    const long long* timesteps, long long* ts, int n_ts, int advance, int n_steps, void* stream);
+/* ldmk_plms_step: plms.py:199-236 -- the eta = 0 update of ldmk_ddim_step (same table row table[4 * *step_idx], same
+ *   optional CFG combine of eps = [uncond | cond], optional pred_x0, x_prev may be x) applied to e', a combination of the
+ *   current and up to three past guidance-combined model outputs.
+ *   hist: device ring [3][n * per_sample] of past outputs; the output of schedule index k lives in slot k % 3 (the index
+ *     walks down by one per step, so slots (k+1)%3, (k+2)%3, (k+3)%3 hold the three outputs before it; nothing is shifted).
+ *   count: device int32, the number of stored outputs, saturating at 3.
+ *   mode 0 (multistep): *count = 0: e' = e_t; 1: (3 e_t - e_1) / 2; 2: (23 e_t - 16 e_1 + 5 e_2) / 12;
+ *     3: (55 e_t - 59 e_1 + 37 e_2 - 9 e_3) / 24, each formed in fp32 in the order written.  e_t is stored in the ring.
+ *     advance: count = min(count + 1, 3), index one down, ts[0..n_ts) = timesteps[index].
+ *   mode 1 (Euler predictor, the first step): x_prev = DDIM update with e_t; x is copied to x_keep (may be NULL: the caller
+ *     kept a copy); e_t is stored in the ring.  advance: ts = timesteps[max(index - 1, 0)] (t_next); index and count stay.
+ *   mode 2 (Euler corrector): eps is the output at t_next; e' = (e_t from the ring + eps) / 2; x is the KEPT latent.  The
+ *     ring keeps e_t.  advance: count = 1, index one down, ts = timesteps[index].
+ *   advance is 0 (step_idx, count and ts are left alone) or 1.  No atomics: results are bitwise reproducible. */
+int ldmk_plms_step(const float* x, const float* eps, const float* table, int* step_idx, int* count, float cfg_scale,
+                   int cfg, int mode, float* hist, float* x_keep, float* x_prev, float* pred_x0, long long per_sample,
+                   int n, const long long* timesteps, long long* ts, int n_ts, int advance, int n_steps, void* stream);
 /* the counter/timestep advance of ldmk_ddim_step on its own (used by the ancestral loop): index -= advance,
  * clamped to [0, n_steps-1]; ts[0..n_ts) = timesteps[index] */
 int ldmk_advance_timestep(int* step_idx, const long long* timesteps, long long* ts, int n_ts, int advance, int n_steps,
