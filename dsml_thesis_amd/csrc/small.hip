@@ -190,6 +190,20 @@ __global__ void timestep_embedding_kernel(const long long* __restrict__ t, const
   if ((dim & 1) && i == 0) emb[(long long)b * dim + dim - 1] = 0.f;
 }
 
+// the same embedding of a REAL-valued timestep (the DPM-Solver's model time, (t - 1/N) 1000): t is used as it is, where the
+// int64 kernel converts first, and everything after that is the same arithmetic -- an integer-valued t gives the same bits
+__global__ void timestep_embedding_f32_kernel(const float* __restrict__ t, const float* __restrict__ freqs,
+                                              float* __restrict__ emb, int n, int dim) {
+  const int half = dim / 2;
+  int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= n * half) return;
+  int b = idx / half, i = idx - b * half;
+  float arg = t[b] * freqs[i];
+  emb[(long long)b * dim + i] = (float)cos((double)arg);
+  emb[(long long)b * dim + half + i] = (float)sin((double)arg);
+  if ((dim & 1) && i == 0) emb[(long long)b * dim + dim - 1] = 0.f;
+}
+
 // ---------------------------------------------------------------------------------------------
 // 3x3 pad-1 convolution from a narrow NCHW input (<= 16 channels, optionally the concat of two
 // tensors) to a wide NHWC output (openaimodel.py:515-517, model.py:394-398,503-507).
@@ -504,6 +518,75 @@ __global__ void plms_advance_kernel(int* step_idx, int* count, const long long* 
     *step_idx = index;
     *count = mode == PLMS_CORRECTOR ? 1 : (c < 3 ? c + 1 : 3);
   }
+}
+
+// ---------------------------------------------------------------------------------------------
+// DPM-Solver++ multistep update (dpm_solver.py:386-399, 526-533, 783-790, 835-849: the data-prediction form, solver type
+// 'dpm_solver', no thresholding).  One row of DPM_ROW floats per step k (the step from t_k to t_{k+1}), made on the host:
+//   0 alpha_s   1 sigma_s   2 order (1, 2 or 3)   3 c_x = sigma_t / sigma_s   4 c_0 = alpha_t (exp(-h) - 1)
+//   5 1/r0   6 1/r1   7 r0 / (r0 + r1)   8 1 / (r0 + r1)   9 c_1   10 c_2   11 the model time of t_{k+1}
+// m0 = (x - sigma_s e) / alpha_s is the data prediction of this step; the predictions of the last three steps live in the ring
+// hist[3][total], step k in slot k % 3, so m1 (step k-1) is in slot (k+2) % 3 and m2 (step k-2) in slot (k+1) % 3: the slot
+// written is never one that is read.  The order comes from the row, not from a count of what is stored, and row 0 is of order 1:
+// after step_idx is reset nothing reads what the ring held before.  Every product, sum and quotient is rounded on its own (no
+// fused multiply-add), in the reference's order.
+enum { DPM_ROW = 12 };
+
+__device__ __forceinline__ int dpm_row_index(const int* step_idx, int n_steps) {
+  int k = *step_idx;                                 // (a captured step replayed past the end stays on the last row)
+  if (k > n_steps - 1) k = n_steps - 1;
+  return k < 0 ? 0 : k;
+}
+
+// (x_prev may be x, so neither is __restrict__)
+__global__ void dpm_step_kernel(const float* x, const float* __restrict__ eps, const float* __restrict__ table,
+                                const int* __restrict__ step_idx, int n_steps, float cfg_scale, int cfg,
+                                float* __restrict__ hist, float* x_prev, float* __restrict__ pred_x0, long long total) {
+  const int k = dpm_row_index(step_idx, n_steps);
+  const float* __restrict__ row = table + (long long)DPM_ROW * k;
+  const float alpha_s = row[0], sigma_s = row[1], c_x = row[3], c_0 = row[4], ir0 = row[5], ir1 = row[6], q = row[7],
+              irs = row[8], c_1 = row[9], c_2 = row[10];
+  const int order = (int)row[2];
+  const float half_c0 = __fmul_rn(0.5f, c_0);
+  float* __restrict__ h0 = hist + (long long)(k % 3) * total;
+  const float* __restrict__ h1 = hist + (long long)((k + 2) % 3) * total;
+  const float* __restrict__ h2 = hist + (long long)((k + 1) % 3) * total;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+    float e;
+    if (cfg) {
+      const float eu = eps[i], ec = eps[total + i];
+      e = __fadd_rn(eu, __fmul_rn(cfg_scale, __fsub_rn(ec, eu)));
+    } else {
+      e = eps[i];
+    }
+    const float xv = x[i];
+    const float m0 = __fdiv_rn(__fsub_rn(xv, __fmul_rn(sigma_s, e)), alpha_s);
+    float xt = __fsub_rn(__fmul_rn(c_x, xv), __fmul_rn(c_0, m0));
+    if (order == 2) {
+      const float d10 = __fmul_rn(ir0, __fsub_rn(m0, h1[i]));
+      xt = __fsub_rn(xt, __fmul_rn(half_c0, d10));
+    } else if (order >= 3) {
+      const float m1 = h1[i];
+      const float d10 = __fmul_rn(ir0, __fsub_rn(m0, m1));
+      const float d11 = __fmul_rn(ir1, __fsub_rn(m1, h2[i]));
+      const float dd = __fsub_rn(d10, d11);
+      const float d1 = __fadd_rn(d10, __fmul_rn(q, dd));
+      const float d2 = __fmul_rn(irs, dd);
+      xt = __fsub_rn(__fadd_rn(xt, __fmul_rn(c_1, d1)), __fmul_rn(c_2, d2));
+    }
+    h0[i] = m0;
+    x_prev[i] = xt;
+    if (pred_x0) pred_x0[i] = m0;
+  }
+}
+
+// runs after dpm_step_kernel on the same stream: ts[0..n_ts) = the model time of t_{k+1} (row k), step_idx one up
+__global__ void dpm_advance_kernel(int* step_idx, const float* __restrict__ table, float* __restrict__ ts, int n_ts, int n_steps) {
+  const int k = dpm_row_index(step_idx, n_steps);
+  const float t = table[(long long)DPM_ROW * k + 11];
+  for (int i = threadIdx.x; i < n_ts; i += blockDim.x) ts[i] = t;
+  __syncthreads();
+  if (threadIdx.x == 0) *step_idx = k + 1;
 }
 
 // ancestral DDPM update (ddpm.py:215-228,1049-1109), per-sample timestep
@@ -861,6 +944,15 @@ extern "C" int ldmk_timestep_embedding(const long long* t, const float* freqs, f
   return check_launch("ldmk_timestep_embedding");
 }
 
+extern "C" int ldmk_timestep_embedding_f32(const float* t, const float* freqs, float* emb, int n, int dim, void* stream) {
+  LDMK_ENTER();
+  LDMK_REQUIRE(t && freqs && emb && n > 0 && dim >= 2, "ldmk_timestep_embedding_f32: bad args");
+  int total = n * (dim / 2);
+  hipLaunchKernelGGL(timestep_embedding_f32_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, t, freqs,
+                     emb, n, dim);
+  return check_launch("ldmk_timestep_embedding_f32");
+}
+
 extern "C" int ldmk_conv3x3_in(const float* x0, int c0, const float* x1, int c1, const float* w, const float* bias,
                                float* out, int n, int h, int w_, int cout, void* stream) {
   LDMK_ENTER();
@@ -967,6 +1059,22 @@ extern "C" int ldmk_plms_step(const float* x, const float* eps, const float* tab
     hipLaunchKernelGGL(plms_advance_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, step_idx, count, timesteps, ts, n_ts,
                        mode, n_steps);
   return check_launch("ldmk_plms_step");
+}
+
+extern "C" int ldmk_dpm_step(const float* x, const float* eps, const float* table, int* step_idx, float cfg_scale, int cfg,
+                             float* hist, float* x_prev, float* pred_x0, long long per_sample, int n, float* ts, int n_ts,
+                             int advance, int n_steps, int max_order, void* stream) {
+  LDMK_ENTER();
+  LDMK_REQUIRE(x && eps && table && step_idx && hist && x_prev, "ldmk_dpm_step: null pointer (x, eps, table, step_idx, hist, x_prev)");
+  LDMK_REQUIRE(per_sample > 0 && n > 0 && n_steps > 0, "ldmk_dpm_step: per_sample, n and n_steps must be positive");
+  LDMK_REQUIRE(max_order >= 1 && max_order <= 3, "ldmk_dpm_step: order %d: the multistep update is built for orders 1, 2 and 3", max_order);
+  if (advance) LDMK_REQUIRE(ts && n_ts > 0 && advance == 1, "ldmk_dpm_step: advance (1: one step on) needs ts/n_ts");
+  long long total = per_sample * n;
+  hipLaunchKernelGGL(dpm_step_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, x, eps, table, step_idx, n_steps,
+                     cfg_scale, cfg, hist, x_prev, pred_x0, total);
+  if (advance)
+    hipLaunchKernelGGL(dpm_advance_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, step_idx, table, ts, n_ts, n_steps);
+  return check_launch("ldmk_dpm_step");
 }
 
 extern "C" int ldmk_advance_timestep(int* step_idx, const long long* timesteps, long long* ts, int n_ts, int advance,

@@ -113,11 +113,12 @@ class DDIMSampler(object):
             return None, cond                    # DiffusionWrapper 'concat': the conditioning is the channel concat (ddpm.py:1407-1409)
         return cond, None
 
-    def _prepare_run(self, cond, shape, x_T, unconditional_guidance_scale, unconditional_conditioning, policy_batch, loops_name):
+    def _prepare_run(self, cond, shape, x_T, unconditional_guidance_scale, unconditional_conditioning, policy_batch, loops_name,
+                     float_time=False):
         """What every sampling loop of this class does before its first step: start noise, conditioning split, guidance
         doubling, 'adm' labels, the launch program (or the patch-wise evaluator) with its conditioning written and its context
         program run, and the per-program dict `loops` that holds loop state under `loops_name` (one name per kind of loop, so the
-        loops never meet each other's state)."""
+        loops never meet each other's state).  `float_time`: the program whose timestep input is the fp32 `t_f32`."""
         dev = self.model.device
         unet = self.model.model.diffusion_model
         b = shape[0]
@@ -150,14 +151,14 @@ class DDIMSampler(object):
             # patch-wise (ddpm.py:904-986): the latent lives in a full-size buffer of nb items ([uncond | cond] under guidance, so
             # ldmk_ddim_step's contract holds); one step = unfold -> the program at batch L*nb -> fold -> the update on the
             # full-size tensors.  Context / concat crops are written once per run.
-            pe = self.model._patched_eval(nb, shape[1], shape[2], shape[3], L_ctx, ncat, policy_batch=policy_nb)
+            pe = self.model._patched_eval(nb, shape[1], shape[2], shape[3], L_ctx, ncat, policy_batch=policy_nb, float_time=float_time)
             pg = pe.pg
             pe.set_cond(ctx_in, cat_in, y_emb)
             x_buf, eps, run_net = pe.x, pe.eps, pe.run
             loops = pe.loops.setdefault(loops_name, {})    # (never the plain loop's state of the same program)
         else:
             unet.policy_batch = policy_nb
-            pg = unet.program(nb, shape[2], shape[3], L_ctx, ncat)
+            pg = unet.program(nb, shape[2], shape[3], L_ctx, ncat, float_time=float_time)
             x_buf, eps, run_net = pg.inputs["x"], pg.outputs["eps"], pg.run
             if L_ctx:
                 pg.inputs["context"].copy_(ctx_in.reshape(nb * L_ctx, -1))

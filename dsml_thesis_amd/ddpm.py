@@ -278,10 +278,11 @@ class LatentDiffusion(_Base):
             raise ValueError(f"split_input_params: a channel-concat conditioning with cond_stage_key {self.cond_stage_key!r}: the "
                              "reference hands every crop the full-size tensor (ddpm.py:973-974) and fails on the shapes")
 
-    def _patched_eval(self, nb, chans, h, w, L_ctx=0, ncat=0, policy_batch="keep"):
+    def _patched_eval(self, nb, chans, h, w, L_ctx=0, ncat=0, policy_batch="keep", float_time=False):
         """The PatchedEval for `nb` full-size (chans,h,w) items under the current split_input_params.  It lives on the launch
         program it drives, so a re-pack of the weights drops it together with that program.  `policy_batch` (the samplers'
-        sharding-invariant tile choice) counts full-size items; the program's batch is that times the number of crops."""
+        sharding-invariant tile choice) counts full-size items; the program's batch is that times the number of crops.
+        `float_time`: over the float-time program (`UNetModel.program`), whose timestep input is the fp32 `t_f32`."""
         from . import patches
         self._patch_cond_check(bool(L_ctx), bool(ncat))
         params = self.split_input_params
@@ -291,7 +292,7 @@ class LatentDiffusion(_Base):
         n_crops = g.ly * g.lx
         if policy_batch != "keep":
             unet.policy_batch = None if policy_batch is None else n_crops * policy_batch
-        pg = unet.program(n_crops * nb, g.ks[0], g.ks[1], L_ctx, ncat)
+        pg = unet.program(n_crops * nb, g.ks[0], g.ks[1], L_ctx, ncat, float_time=float_time)
         key = (nb, chans, h, w, g.ks, g.stride) + patches.params_key(params)
         cache = pg.__dict__.setdefault("_patched", {})
         if key not in cache:
@@ -319,7 +320,7 @@ class LatentDiffusion(_Base):
         L_ctx = 0 if ctx is None else ctx.shape[1]
         ncat = 0 if cat is None else cat.shape[1]
         for _ in range(MAX_ARITHMETIC_PASSES):
-            pe = self._patched_eval(nb, chans, h, w, L_ctx, ncat)
+            pe = self._patched_eval(nb, chans, h, w, L_ctx, ncat, float_time=t.is_floating_point())
             pe.x.copy_(x_noisy)
             pe.set_t(t)
             pe.set_cond(ctx, cat, y_emb)

@@ -137,6 +137,7 @@ _SIGS = {
     "ldmk_softmax_rows": (C.c_int, [_fp, C.c_longlong, C.c_int, C.c_float, _fp]),
     "ldmk_dense_small": (C.c_int, [_fp, C.c_int, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
     "ldmk_timestep_embedding": (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_int, _fp]),
+    "ldmk_timestep_embedding_f32": (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_int, _fp]),
     "ldmk_conv3x3_in": (C.c_int, [_fp, C.c_int, _fp, C.c_int, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
     "ldmk_conv3x3_out": (C.c_int, [_fp, _fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
     "ldmk_conv3x3_out_small": (C.c_int, [_fp, _fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
@@ -145,6 +146,8 @@ _SIGS = {
                                  C.c_int, C.c_int, C.c_int, _fp]),
     "ldmk_plms_step": (C.c_int, [_fp, _fp, _fp, _fp, _fp, C.c_float, C.c_int, C.c_int, _fp, _fp, _fp, _fp, C.c_longlong, C.c_int,
                                  _fp, _fp, C.c_int, C.c_int, C.c_int, _fp]),
+    "ldmk_dpm_step": (C.c_int, [_fp, _fp, _fp, _fp, C.c_float, C.c_int, _fp, _fp, _fp, C.c_longlong, C.c_int, _fp, C.c_int, C.c_int,
+                                C.c_int, C.c_int, _fp]),
     "ldmk_advance_timestep": (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_int, C.c_int, _fp]),
     "ldmk_ddpm_step": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_longlong, C.c_int, _fp]),
     "ldmk_patch_unfold": (C.c_int, [_fp, _fp] + [C.c_int] * 10 + [_fp]),

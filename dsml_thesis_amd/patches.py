@@ -161,7 +161,10 @@ class PatchedEval:
         pg.ctx_program.run()
 
     def set_t(self, t):
-        self.pg.inputs["t"].copy_(t.to(torch.int64).repeat(self.L))
+        if "t_f32" in self.pg.inputs:                      # the float-time program: a real-valued time, embedded as it is
+            self.pg.inputs["t_f32"].copy_(t.to(torch.float32).repeat(self.L))
+        else:
+            self.pg.inputs["t"].copy_(t.to(torch.int64).repeat(self.L))
 
     def run(self):
         """x -> eps: unfold, the program at batch L*nb, fold.  Stream launches only."""

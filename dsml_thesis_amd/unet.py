@@ -819,7 +819,7 @@ class UNetModel(nn.Module):
                 yield f"output_blocks.{i}.{j}.", m
 
     # ---- program construction ---------------------------------------------------------------------
-    def _build(self, n, H, W_, L_ctx, c_concat, policy_n):
+    def _build(self, n, H, W_, L_ctx, c_concat, policy_n, float_time=False):
         P, sd = self._packed, self._sd
         dev = next(self.parameters()).device
         if self.resblock_updown and (H % (1 << (len(self.channel_mult) - 1)) or W_ % (1 << (len(self.channel_mult) - 1))):
@@ -833,10 +833,11 @@ class UNetModel(nn.Module):
         cx = self.in_channels - c_concat
         x_in = pg.alloc(n, cx, H, W_)
         cc_in = pg.alloc(n, c_concat, H, W_) if c_concat else None
-        t_in = pg.alloc(n, dtype=torch.int64)
+        # float_time: the timestep input is real-valued, fp32 under the name `t_f32` (the DPM-Solver's model time); nothing else differs
+        t_in = pg.alloc(n, dtype=torch.float32 if float_time else torch.int64)
         ctx_in = pg.alloc(n * L_ctx, self.context_dim) if L_ctx else None      # (unconditional UNet: no context)
         y_emb = pg.alloc(n, emb_ch) if self.num_classes is not None else None     # label_emb(y) rows, gathered by forward()
-        pg.inputs = dict(x=x_in, c_concat=cc_in, t=t_in, context=ctx_in, y_emb=y_emb)
+        pg.inputs = {"x": x_in, "c_concat": cc_in, "t_f32" if float_time else "t": t_in, "context": ctx_in, "y_emb": y_emb}
         ctx_pg = Program(dev)     # context-only work: re-run only when the context changes
         ctx_pg._all = pg._all     # share accounting
         p_ = lambda t: 0 if t is None else t.data_ptr()
@@ -844,7 +845,7 @@ class UNetModel(nn.Module):
 
         # -- time embedding MLP + all emb_layers (one launch each)
         temb = pg.alloc(n, mc)
-        pg.add("ldmk_timestep_embedding", p_(t_in), p_(P["freqs"]), p_(temb), n, mc)
+        pg.add("ldmk_timestep_embedding_f32" if float_time else "ldmk_timestep_embedding", p_(t_in), p_(P["freqs"]), p_(temb), n, mc)
         e1 = pg.alloc(n, emb_ch)
         pg.add("ldmk_dense_small", p_(temb), mc, p_(P["te0"]), p_(sd["time_embed.0.bias"]), p_(e1), emb_ch, n, mc, emb_ch, 0)
         emb = pg.alloc(n, emb_ch)
@@ -1056,20 +1057,23 @@ class UNetModel(nn.Module):
                 "denied": sorted(self._sites.denied) if self._sites is not None else [], "flags_up": up,
                 "ln_flag_up": bool(self._ln_flag is not None and int(self._ln_flag.item()) != 0), "ln_unfolded": bool(self.ln_unfolded)}
 
-    def program(self, n, H, W_, L_ctx, c_concat=0):
+    def program(self, n, H, W_, L_ctx, c_concat=0, float_time=False):
+        """The launch program of this shape.  float_time: the variant whose timestep input is `inputs["t_f32"]`, fp32 and
+        real-valued, embedded by ldmk_timestep_embedding_f32 -- a program of its own under its own key (a recorded launch holds
+        the pointer and the element type of its input), over the same packed weights and tile plans as the integer one."""
         if self._packed is None or (self.auto_repack and self._pack_sig != self._signature()):
             self.pack_weights()
         policy_n = self.policy_batch or n
-        key = (n, H, W_, L_ctx, c_concat, policy_n)
+        key = (n, H, W_, L_ctx, c_concat, policy_n) + (("float_time",) if float_time else ())
         pg = self._programs.get(key)
         if pg is None:
             from . import unet_small
             plain = self._heads32 and not self.use_scale_shift_norm and self.num_classes is None and not self.resblock_updown
             if plain and unet_small.wants_small_route(policy_n, H, W_, L_ctx):
                 # batch 1-2 (the reference's shipped talking-face mode): the program cut for few dependent launches
-                pg = unet_small.build_small(self, n, H, W_, L_ctx, c_concat, policy_n)
+                pg = unet_small.build_small(self, n, H, W_, L_ctx, c_concat, policy_n, float_time=float_time)
             else:
-                pg = self._build(n, H, W_, L_ctx, c_concat, policy_n)
+                pg = self._build(n, H, W_, L_ctx, c_concat, policy_n, float_time=float_time)
             self._programs[key] = pg
         return pg
 
@@ -1083,7 +1087,8 @@ class UNetModel(nn.Module):
 
     @torch.no_grad()
     def forward(self, x, timesteps=None, context=None, y=None, c_concat=None, **kwargs):
-        """x: (N, C, H, W) fp32 NCHW; timesteps: (N,) int64; context: (N, L, context_dim).
+        """x: (N, C, H, W) fp32 NCHW; timesteps: (N,) integer, or floating point for a real-valued time (embedded as it is, like
+        the reference's `timesteps[:, None].float() * freqs`, util.py:161-165: the float-time program); context: (N, L, context_dim).
         `c_concat` (N, C2, H, W) is concatenated to x on the channel axis inside the first conv (the TF
         DiffusionWrapper does `torch.cat([x] + c_concat, 1)`, ddpm2cond.py:1309); passing an already
         concatenated x works too."""
@@ -1100,12 +1105,16 @@ class UNetModel(nn.Module):
         assert cx + cc == self.in_channels, f"got {cx}+{cc} input channels, model has {self.in_channels}"
         assert context is None or (context.shape[0] == n and context.shape[2] == self.context_dim)
         L_ctx = 0 if context is None else context.shape[1]
+        float_time = timesteps.is_floating_point()
         for _ in range(MAX_ARITHMETIC_PASSES):
-            pg = self.program(n, H, W_, L_ctx, cc)
+            pg = self.program(n, H, W_, L_ctx, cc, float_time=float_time)
             pg.inputs["x"].copy_(x)
             if cc:
                 pg.inputs["c_concat"].copy_(c_concat)
-            pg.inputs["t"].copy_(timesteps.to(torch.int64))
+            if float_time:
+                pg.inputs["t_f32"].copy_(timesteps.to(torch.float32))
+            else:
+                pg.inputs["t"].copy_(timesteps.to(torch.int64))
             if L_ctx:
                 pg.inputs["context"].copy_(context.reshape(n * L_ctx, self.context_dim))
             if y is not None:

@@ -138,7 +138,7 @@ class SmallBuilder:
         return x.raw
 
 
-def build_small(unet, n, H, W_, L_ctx, c_concat, policy_n):
+def build_small(unet, n, H, W_, L_ctx, c_concat, policy_n, float_time=False):
     assert L_ctx == 1
     pack_small(unet)
     # ldmk_dense_small's 16-byte-load form (<= 4 batch rows per launch): requested from the JOB's batch, so that every shard of
@@ -152,9 +152,9 @@ def build_small(unet, n, H, W_, L_ctx, c_concat, policy_n):
     cx = unet.in_channels - c_concat
     x_in = pg.alloc(n, cx, H, W_)
     cc_in = pg.alloc(n, c_concat, H, W_) if c_concat else None
-    t_in = pg.alloc(n, dtype=torch.int64)
+    t_in = pg.alloc(n, dtype=torch.float32 if float_time else torch.int64)      # float_time: as in UNetModel._build
     ctx_in = pg.alloc(n * L_ctx, unet.context_dim)
-    pg.inputs = dict(x=x_in, c_concat=cc_in, t=t_in, context=ctx_in)
+    pg.inputs = {"x": x_in, "c_concat": cc_in, "t_f32" if float_time else "t": t_in, "context": ctx_in}
     ctx_pg = Program(dev)
     ctx_pg._all = pg._all
     p_ = lambda t: 0 if t is None else (t if isinstance(t, int) else t.data_ptr())
@@ -165,7 +165,7 @@ def build_small(unet, n, H, W_, L_ctx, c_concat, policy_n):
     # them as a parallel branch of the captured step -- a forked stream, engine.Program.side_calls -- was measured: the
     # fork / join inside the hipGraph costs more than the 45 us it hides, 2265 -> 2423 us per step.  Kept in line.)
     temb = pg.alloc(n, mc)
-    pg.add("ldmk_timestep_embedding", p_(t_in), p_(P["freqs"]), p_(temb), n, mc)
+    pg.add("ldmk_timestep_embedding_f32" if float_time else "ldmk_timestep_embedding", p_(t_in), p_(P["freqs"]), p_(temb), n, mc)
     e1 = pg.alloc(n, emb_ch)
     pg.add("ldmk_dense_small", p_(temb), mc, p_(P["te0"]), p_(sd["time_embed.0.bias"]), p_(e1), emb_ch, n, mc, emb_ch, ds4)
     emb = pg.alloc(n, emb_ch)

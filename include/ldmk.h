@@ -495,6 +495,9 @@ int ldmk_dense_small(const float* x, int ldx, const float* w, const float* bias,
 /* timestep_embedding, util.py:151-171: t int64 [n] -> emb [n][dim] = [cos(t*f) | sin(t*f)];
  * freqs[dim/2] = exp(-ln(max_period) * i / (dim/2)) is a per-model constant computed once on the host */
 int ldmk_timestep_embedding(const long long* t, const float* freqs, float* emb, int n, int dim, void* stream);
+/* the same for a real-valued timestep, t float32 [n] (the DPM-Solver's model time (t - 1/N) 1000, dpm_solver.py:278-287):
+ * arg = t * f in fp32, cos and sin in double, rounded once -- an integer-valued t gives the bits of the int64 entry point */
+int ldmk_timestep_embedding_f32(const float* t, const float* freqs, float* emb, int n, int dim, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Narrow-channel convolutions at the NCHW latent boundary.
@@ -553,6 +556,25 @@ int ldmk_ddim_step(const float* x, const float* eps, const float* noise, const f
 int ldmk_plms_step(const float* x, const float* eps, const float* table, int* step_idx, int* count, float cfg_scale,
                    int cfg, int mode, float* hist, float* x_keep, float* x_prev, float* pred_x0, long long per_sample,
                    int n, const long long* timesteps, long long* ts, int n_ts, int advance, int n_steps, void* stream);
+/* ldmk_dpm_step: the multistep DPM-Solver++ update (dpm_solver.py:386-399, 526-533, 783-790, 835-849: data prediction, solver
+ *   type 'dpm_solver', no thresholding), orders 1-3.  table: [n_steps][12] float32, row k = the step from t_k to t_{k+1}:
+ *     0 alpha_s  1 sigma_s  2 order  3 c_x = sigma_t / sigma_s  4 c_0 = alpha_t (exp(-h) - 1)  5 1/r0  6 1/r1  7 r0 / (r0 + r1)
+ *     8 1 / (r0 + r1)  9 c_1  10 c_2  11 the model time of t_{k+1}.
+ *   step_idx: device int32, the CURRENT step k (read clamped to [0, n_steps - 1]).  Per element: e = e_u + scale (e_c - e_u) when
+ *   cfg (eps = [uncond | cond], 2n items), m0 = (x - sigma_s e) / alpha_s, stored in the ring and in pred_x0 (may be NULL);
+ *     order 1: x' = c_x x - c_0 m0
+ *     order 2: D1_0 = (1/r0)(m0 - m1);  x' = c_x x - c_0 m0 - (0.5 c_0) D1_0
+ *     order 3: D1_0 as above, D1_1 = (1/r1)(m1 - m2), D1 = D1_0 + r0/(r0+r1) (D1_0 - D1_1), D2 = 1/(r0+r1) (D1_0 - D1_1);
+ *              x' = c_x x - c_0 m0 + c_1 D1 - c_2 D2
+ *   in fp32, every operation rounded on its own, in the order written.  x_prev may be x.
+ *   hist: device ring [3][n * per_sample]; step k's m0 lives in slot k % 3, m1 / m2 are those of steps k-1 / k-2.  The order is
+ *     read from the row, never from a count: row 0 is of order 1, so after step_idx is set to 0 the ring's contents are dead.
+ *   max_order: the highest order any row of the table names; outside 1..3 the call is refused (the host built the table).
+ *   advance is 0 or 1: ts[0..n_ts) (float32, the UNet program's `t_f32` input; n_ts need not be n) = row k's model time, then
+ *   step_idx = k + 1.  No atomics: results are bitwise reproducible. */
+int ldmk_dpm_step(const float* x, const float* eps, const float* table, int* step_idx, float cfg_scale, int cfg, float* hist,
+                  float* x_prev, float* pred_x0, long long per_sample, int n, float* ts, int n_ts, int advance, int n_steps,
+                  int max_order, void* stream);
 /* the counter/timestep advance of ldmk_ddim_step on its own (used by the ancestral loop): index -= advance,
  * clamped to [0, n_steps-1]; ts[0..n_ts) = timesteps[index] */
 int ldmk_advance_timestep(int* step_idx, const long long* timesteps, long long* ts, int n_ts, int advance, int n_steps,
