@@ -6,7 +6,7 @@ Decoder, model.py:462-568) and `encode` (Encoder -> quant_conv, model.py:368-459
 double-width head produces (one kernel, ldmk_conv3x3_moments), `decode` = post_quant_conv -> Decoder.
 `IdentityFirstStage` (autoencoder.py:426-443): pixels are the latents.
 `VQModel`: the trainable sibling of `VQModelInterface` (training_step, optimisers, EMA; train_first_stage.py).
-Training-side members of `AutoencoderKL` are out of scope.
+`AutoencoderKL` carries its training surface itself; what the two trainable classes share is `_Trainable`.
 
 Parameter trees and state-dict keys equal the reference's (`encoder.*`, `decoder.*`, `quant_conv.*`,
 `post_quant_conv.*`, and `quantize.embedding.weight` for the VQ model).  Forward passes are launch programs over
@@ -475,36 +475,22 @@ class _AdamOfTrainer:
         self.model.trainer().P.grad.zero_()
 
 
-class VQModel(_VQFirstStage):
-    """ldm.models.autoencoder.VQModel (autoencoder.py:14-262) and taming.models.vqgan.VQModel as a trainable drop-in, without
-    Lightning: `training_step(batch, batch_idx, optimizer_idx)` runs the whole autoencoder step on the HIP kernels
-    (train_first_stage.FirstStageTrainer) and returns the loss; `configure_optimizers()` hands out the two optimizers, and
-    `train_batch(batch)` is the loop body Lightning would run (autoencoder step, discriminator step, EMA).  The trained
-    weights live in the trainer's arena and are written back into the nn.Parameters whenever an inference method, the state
-    dict or the EMA scope needs them.  The loss module is not a registered submodule (the first-stage machinery walks
-    `parameters()`); `state_dict()` / `load_state_dict()` carry it under the reference's `loss.` prefix all the same.
-    With use_ema the shadow is a flat copy of the arena (not part of the state dict)."""
+class _Trainable:
+    """What the trainable first stages (VQModel, AutoencoderKL) share, mixed in ahead of their `_FirstStage` base: the loss
+    module kept out of the module tree but carried in the state dict under `loss.`, the lazily built
+    `train_first_stage.FirstStageTrainer` whose arena runs ahead of the nn.Parameters (`_dirty`) and is written back by
+    `_ensure` before any inference method, state-dict read or EMA scope, the logging stand-ins for Lightning's, the two
+    optimizers, and `train_batch`, the loop body Lightning would run.  A subclass supplies `training_step`."""
 
-    def __init__(self, ddconfig, lossconfig, n_embed, embed_dim, ckpt_path=None, ignore_keys=[], image_key="image",
-                 colorize_nlabels=None, monitor=None, batch_resize_range=None, scheduler_config=None, lr_g_factor=1.0,
-                 remap=None, sane_index_shape=False, use_ema=False):
-        for name, v in (("batch_resize_range", batch_resize_range), ("remap", remap), ("colorize_nlabels", colorize_nlabels),
-                        ("scheduler_config", scheduler_config)):
-            if v is not None:
-                raise NotImplementedError(f"VQModel: {name} is not built")
-        super().__init__(embed_dim, ddconfig=ddconfig, n_embed=n_embed, image_key=image_key, monitor=monitor,
-                         sane_index_shape=sane_index_shape)
+    def _init_training(self, lossconfig, lr_g_factor=1.0, use_ema=False):
         from .util import instantiate_from_config
-        loss = lossconfig if isinstance(lossconfig, nn.Module) else instantiate_from_config(lossconfig)
-        object.__setattr__(self, "_loss", loss)            # kept out of the module tree (see the class docstring)
+        loss = lossconfig if isinstance(lossconfig, nn.Module) or lossconfig is None else instantiate_from_config(lossconfig)
+        object.__setattr__(self, "_loss", loss)            # kept out of the module tree (the first-stage machinery walks parameters())
         self.lr_g_factor, self.use_ema = lr_g_factor, use_ema
         self.learning_rate, self.global_step = 4.5e-6, 0
         self.logged = {}
         self._tr, self._dirty, self._shadow, self._ema_updates, self._opts = None, False, None, 0, None
-        if ckpt_path is not None:
-            self.init_from_ckpt(ckpt_path, ignore_keys=ignore_keys)
 
-    # ---- plumbing -----------------------------------------------------------------------------------------------
     @property
     def loss(self):
         return self._loss
@@ -558,31 +544,6 @@ class VQModel(_VQFirstStage):
     def log(self, k, v, **kw):
         self.log_dict({k: v})
 
-    # ---- the reference's surface -----------------------------------------------------------------------------------
-    def encode(self, x):
-        from . import train_ops as T
-        h = self._run_encode(x)
-        quant, idx = ops.vq_nearest(h, self.quantize.embedding.weight.detach())
-        emb_loss, _ = T.vq_loss_bwd(h, self.quantize.embedding.weight.detach(), idx.reshape(-1), beta=self.quantize.beta,
-                                    want_dz=False)
-        ind = idx.long().reshape(x.shape[0], h.shape[2], h.shape[3]) if self.quantize.sane_index_shape else idx.long().reshape(-1)
-        return quant, emb_loss, (None, None, ind)
-
-    def encode_to_prequant(self, x):
-        return self._run_encode(x)
-
-    def decode(self, quant):
-        return self._run_decode(quant, False)
-
-    def decode_code(self, code_b):
-        b, h, w = code_b.shape
-        return self.decode(self.quantize.get_codebook_entry(code_b, (b, h, w, self.embed_dim)))
-
-    def forward(self, input, return_pred_indices=False):
-        quant, diff, (_, _, ind) = self.encode(input)
-        dec = self.decode(quant)
-        return (dec, diff, ind) if return_pred_indices else (dec, diff)
-
     def get_input(self, batch, k):
         x = batch[k]
         if len(x.shape) == 3:
@@ -591,26 +552,6 @@ class VQModel(_VQFirstStage):
 
     def get_last_layer(self):
         return self.decoder.conv_out.weight
-
-    def training_step(self, batch, batch_idx, optimizer_idx):
-        """optimizer_idx 0: forward, loss, ONE backward through the autoencoder (gradients in trainer().P.grad), -> aeloss.
-        optimizer_idx 1: forward again (the autoencoder may have stepped, as under Lightning), -> the discriminator loss with
-        autograd attached to the discriminator."""
-        from .losses import perplexity_from_counts
-        x = self.get_input(batch, self.image_key).to(next(self.parameters()).device)
-        tr, loss = self.trainer(), self.loss
-        loss.discriminator.train()
-        xrec = tr.forward(x)
-        if optimizer_idx == 0:
-            aeloss, log = loss(tr.qloss, x, xrec, 0, self.global_step, last_layer=tr.last_layer_grad, split="train")
-            tr.backward(loss.d_image, codebook_weight=loss.codebook_weight)
-            log["train/perplexity"], log["train/cluster_usage"] = perplexity_from_counts(tr.counts)
-            self.log_dict(log)
-            return aeloss
-        tr.tape = []
-        discloss, log = loss(tr.qloss, x, xrec, 1, self.global_step, split="train")
-        self.log_dict(log)
-        return discloss
 
     def configure_optimizers(self):
         lr_d, lr_g = self.learning_rate, self.lr_g_factor * self.learning_rate
@@ -648,6 +589,75 @@ class VQModel(_VQFirstStage):
             if self.use_ema:
                 self._tr.sync_to_module()
 
+
+class VQModel(_Trainable, _VQFirstStage):
+    """ldm.models.autoencoder.VQModel (autoencoder.py:14-262) and taming.models.vqgan.VQModel as a trainable drop-in, without
+    Lightning: `training_step(batch, batch_idx, optimizer_idx)` runs the whole autoencoder step on the HIP kernels
+    (train_first_stage.FirstStageTrainer) and returns the loss; `configure_optimizers()` hands out the two optimizers, and
+    `train_batch(batch)` is the loop body Lightning would run (autoencoder step, discriminator step, EMA).  The trained
+    weights live in the trainer's arena and are written back into the nn.Parameters whenever an inference method, the state
+    dict or the EMA scope needs them.  The loss module is not a registered submodule (the first-stage machinery walks
+    `parameters()`); `state_dict()` / `load_state_dict()` carry it under the reference's `loss.` prefix all the same.
+    With use_ema the shadow is a flat copy of the arena (not part of the state dict)."""
+
+    def __init__(self, ddconfig, lossconfig, n_embed, embed_dim, ckpt_path=None, ignore_keys=[], image_key="image",
+                 colorize_nlabels=None, monitor=None, batch_resize_range=None, scheduler_config=None, lr_g_factor=1.0,
+                 remap=None, sane_index_shape=False, use_ema=False):
+        for name, v in (("batch_resize_range", batch_resize_range), ("remap", remap), ("colorize_nlabels", colorize_nlabels),
+                        ("scheduler_config", scheduler_config)):
+            if v is not None:
+                raise NotImplementedError(f"VQModel: {name} is not built")
+        super().__init__(embed_dim, ddconfig=ddconfig, n_embed=n_embed, image_key=image_key, monitor=monitor,
+                         sane_index_shape=sane_index_shape)
+        self._init_training(lossconfig, lr_g_factor, use_ema)
+        if ckpt_path is not None:
+            self.init_from_ckpt(ckpt_path, ignore_keys=ignore_keys)
+
+    # ---- the reference's surface -----------------------------------------------------------------------------------
+    def encode(self, x):
+        from . import train_ops as T
+        h = self._run_encode(x)
+        quant, idx = ops.vq_nearest(h, self.quantize.embedding.weight.detach())
+        emb_loss, _ = T.vq_loss_bwd(h, self.quantize.embedding.weight.detach(), idx.reshape(-1), beta=self.quantize.beta,
+                                    want_dz=False)
+        ind = idx.long().reshape(x.shape[0], h.shape[2], h.shape[3]) if self.quantize.sane_index_shape else idx.long().reshape(-1)
+        return quant, emb_loss, (None, None, ind)
+
+    def encode_to_prequant(self, x):
+        return self._run_encode(x)
+
+    def decode(self, quant):
+        return self._run_decode(quant, False)
+
+    def decode_code(self, code_b):
+        b, h, w = code_b.shape
+        return self.decode(self.quantize.get_codebook_entry(code_b, (b, h, w, self.embed_dim)))
+
+    def forward(self, input, return_pred_indices=False):
+        quant, diff, (_, _, ind) = self.encode(input)
+        dec = self.decode(quant)
+        return (dec, diff, ind) if return_pred_indices else (dec, diff)
+
+    def training_step(self, batch, batch_idx, optimizer_idx):
+        """optimizer_idx 0: forward, loss, ONE backward through the autoencoder (gradients in trainer().P.grad), -> aeloss.
+        optimizer_idx 1: forward again (the autoencoder may have stepped, as under Lightning), -> the discriminator loss with
+        autograd attached to the discriminator."""
+        from .losses import perplexity_from_counts
+        x = self.get_input(batch, self.image_key).to(next(self.parameters()).device)
+        tr, loss = self.trainer(), self.loss
+        loss.discriminator.train()
+        xrec = tr.forward(x)
+        if optimizer_idx == 0:
+            aeloss, log = loss(tr.qloss, x, xrec, 0, self.global_step, last_layer=tr.last_layer_grad, split="train")
+            tr.backward(loss.d_image, codebook_weight=loss.codebook_weight)
+            log["train/perplexity"], log["train/cluster_usage"] = perplexity_from_counts(tr.counts)
+            self.log_dict(log)
+            return aeloss
+        tr.tape = []
+        discloss, log = loss(tr.qloss, x, xrec, 1, self.global_step, split="train")
+        self.log_dict(log)
+        return discloss
+
     @torch.no_grad()
     def _validation_step(self, batch, batch_idx, suffix=""):
         x = self.get_input(batch, self.image_key).to(next(self.parameters()).device)
@@ -680,16 +690,22 @@ class VQModel(_VQFirstStage):
         return log
 
 
-class AutoencoderKL(_FirstStage):
-    """autoencoder.py:285-342 as LatentDiffusion uses it.  The encoder ends in a 3x3 convolution to 2*z_channels moment
-    channels and a 1x1 `quant_conv` to 2*embed_dim: both run in one kernel (ldmk_conv3x3_moments), which is built for up to
-    8 channels on either side -- z_channels, embed_dim <= 4, i.e. the KL-f4 and KL-f8 autoencoders."""
+class AutoencoderKL(_Trainable, _FirstStage):
+    """autoencoder.py:285-423.  The encoder ends in a 3x3 convolution to 2*z_channels moment channels and a 1x1 `quant_conv`
+    to 2*embed_dim: at inference both run in one kernel (ldmk_conv3x3_moments), which is built for up to 8 channels on either
+    side -- z_channels, embed_dim <= 4, i.e. the KL-f4 and KL-f8 autoencoders.
+    Training, without Lightning as for VQModel: under a `losses.LPIPSWithDiscriminator` lossconfig,
+    `training_step(batch, batch_idx, optimizer_idx)` runs the autoencoder step on the HIP kernels
+    (train_first_stage.FirstStageTrainer, KL bottleneck) and `train_batch(batch)` is the two-optimizer loop body.  Each
+    `training_step` call draws the posterior once, from `sample_noise`.  With `lossconfig = torch.nn.Identity` (every
+    LatentDiffusion config) nothing of that is built and `training_step` raises.  `use_ema` is this project's addition (the
+    reference's AutoencoderKL has none): a flat shadow of the arena, as VQModel's."""
 
     NARROW_KEYS = ("encoder.conv_out.weight",)
     MAX_Z = 4
 
     def __init__(self, ddconfig, lossconfig, embed_dim, ckpt_path=None, ignore_keys=[], image_key="image",
-                 colorize_nlabels=None, monitor=None):
+                 colorize_nlabels=None, monitor=None, use_ema=False):
         super().__init__()
         ddconfig = dict(ddconfig)
         assert ddconfig["double_z"]
@@ -708,7 +724,10 @@ class AutoencoderKL(_FirstStage):
             self.register_buffer("colorize", torch.randn(3, colorize_nlabels, 1, 1))
         if monitor is not None:
             self.monitor = monitor
-        self._finish_init(ckpt_path, ignore_keys)
+        self._finish_init(None, ignore_keys)
+        self._init_training(lossconfig, use_ema=use_ema)
+        if ckpt_path is not None:
+            self.init_from_ckpt(ckpt_path, ignore_keys=ignore_keys)
 
     def _build_encode(self, n, H, W_):
         e, P, sd = self.encoder, self._packed, self._sd
@@ -741,10 +760,68 @@ class AutoencoderKL(_FirstStage):
         pg.run()
         return pg.outputs["image"].clone()
 
+    def sample_noise(self, shape):
+        """The one source of every normal draw of this class (posterior samples of `forward` and of the training forward, the
+        latents of `log_images`); tests and fixtures override it."""
+        return torch.randn(tuple(shape), device=next(self.parameters()).device, dtype=torch.float32)
+
     def forward(self, input, sample_posterior=True):
         posterior = self.encode(input)
-        z = posterior.sample() if sample_posterior else posterior.mode()
+        z = posterior.sample(noise=self.sample_noise(posterior.mean.shape)) if sample_posterior else posterior.mode()
         return self.decode(z), posterior
+
+    # ---- the training surface (autoencoder.py:344-415) --------------------------------------------------------------
+    def _training_loss(self):
+        loss = self.loss
+        if not (isinstance(loss, nn.Module) and hasattr(loss, "discriminator") and hasattr(loss, "kl_weight")):
+            raise L.LdmkError(f"AutoencoderKL.training_step: lossconfig gave {type(loss).__name__}, which is no training loss; "
+                              "construct the model with ldm.modules.losses.LPIPSWithDiscriminator to train it")
+        return loss
+
+    def training_step(self, batch, batch_idx, optimizer_idx):
+        """optimizer_idx 0: forward (one posterior draw), loss, ONE backward through the autoencoder (gradients in
+        trainer().P.grad), -> aeloss.  optimizer_idx 1: forward again with a draw of its own (the autoencoder may have stepped,
+        as under Lightning), -> the discriminator loss with autograd attached to the discriminator."""
+        loss = self._training_loss()
+        x = self.get_input(batch, self.image_key).to(next(self.parameters()).device)
+        tr = self.trainer()
+        loss.discriminator.train()
+        xrec = tr.forward(x)
+        if optimizer_idx == 0:
+            aeloss, log = loss(x, xrec, tr.kl, 0, self.global_step, last_layer=tr.last_layer_grad, split="train")
+            tr.backward(loss.d_image, kl_weight=loss.kl_weight)
+            self.log("aeloss", aeloss)
+            self.log_dict(log)
+            return aeloss
+        tr.tape = []
+        discloss, log = loss(x, xrec, tr.kl, 1, self.global_step, split="train")
+        self.log("discloss", discloss)
+        self.log_dict(log)
+        return discloss
+
+    @torch.no_grad()
+    def validation_step(self, batch, batch_idx):
+        loss = self._training_loss()
+        x = self.get_input(batch, self.image_key).to(next(self.parameters()).device)
+        xrec, posterior = self(x)
+        loss.discriminator.eval()
+        _, log_ae = loss(x, xrec, posterior, 0, self.global_step, last_layer=None, split="val")
+        _, log_disc = loss(x, xrec, posterior, 1, self.global_step, split="val")
+        self.log_dict(log_ae)
+        self.log_dict(log_disc)
+        return dict(log_ae, **log_disc)
+
+    @torch.no_grad()
+    def log_images(self, batch, only_inputs=False, **kwargs):
+        x = self.get_input(batch, self.image_key).to(next(self.parameters()).device)
+        if x.shape[1] > 3:
+            raise NotImplementedError("AutoencoderKL.log_images: the random colorize projection of segmentation inputs is not built")
+        log = dict(inputs=x)
+        if not only_inputs:
+            xrec, posterior = self(x)
+            log["samples"] = self.decode(self.sample_noise(posterior.mean.shape))
+            log["reconstructions"] = xrec
+        return log
 
 
 class IdentityFirstStage(nn.Module):

@@ -4,8 +4,10 @@
 `parameters` are the encoder's moments (n, 2e, h, w): mean on channels [0, e), log-variance on [e, 2e).  On the GPU the
 clamped log-variance, `std`, `var` and the sample all come from one elementwise kernel (`ldmk_gauss_posterior`); the three
 tensors are produced together the first time one of them is read, a sample alone never materialises them.  `kl` and `nll`
-are used by first-stage training only (out of scope) and are a few lines of torch over those tensors.  Moments on the CPU
-(fixtures, host-side checks of `kl` / `nll`) get the same attributes from torch; sampling needs the GPU.
+are a few lines of torch over those tensors: the validation step of first-stage training reads `kl` from here, while the
+training step takes the draw, the per-sample KL and their gradient from its own kernels (ldmk_gauss_kl_fwd / _bwd,
+train_first_stage.py).  Moments on the CPU (fixtures, host-side checks of `kl` / `nll`) get the same attributes
+from torch; sampling needs the GPU.
 """
 import math
 

@@ -219,6 +219,10 @@ _SIGS = {
                                         _fp]),
     "ldmk_conv1x1_nchw_bwd": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp]),
     "ldmk_l1_grad": (C.c_int, [_fp, _fp, _fp, C.c_longlong, C.c_longlong, _fp, _fp, _fp]),
+    # ---- first-stage (KL) training
+    "ldmk_gauss_kl_fwd": (C.c_int, [_fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp]),
+    "ldmk_gauss_kl_bwd": (C.c_int, [_fp, _fp, _fp, C.c_float, _fp, C.c_int, C.c_int, C.c_int, _fp]),
+    "ldmk_l1_sum_grad": (C.c_int, [_fp, _fp, _fp, C.c_longlong, C.c_float, _fp, _fp, _fp]),
 }
 # every symbol include/ldmk.h declares (checked by tests/test_abi.py against the header text)
 EXPORTED = [k for k in _SIGS if k not in ("ldmk_igemm_force_config", "ldmk_attn_force_qt")]

@@ -1,4 +1,5 @@
-"""The VQGAN training loss (ldm/modules/losses/vqperceptual.py:43-167; taming/modules/discriminator/model.py:17-67).
+"""The first-stage training losses: the VQGAN's (ldm/modules/losses/vqperceptual.py:43-167) and the KL autoencoder's
+(ldm/modules/losses/contperceptual.py:7-110); the PatchGAN of both (taming/modules/discriminator/model.py:17-67).
 
 `VQLPIPSWithDiscriminator` turns a reconstruction into the image gradient `FirstStageTrainer.backward` takes.  The pixel
 term runs on ldmk_l1_grad / ldmk_mse_grad; the PatchGAN discriminator and the perceptual network are plain torch modules on
@@ -10,7 +11,12 @@ One backward per autoencoder step:
     loss    = nll + d_weight * disc_factor * g + codebook_weight * qloss,   nll = mean(pixel + perceptual_weight * p)
     d_image = d nll / d xrec + d_weight * disc_factor * d g / d xrec
     d_weight = clamp(|d nll / d W_last| / (|d g / d W_last| + 1e-4), 0, 1e4) * disc_weight
-where the two last-layer gradients come from `last_layer(d_image_term)` -- `FirstStageTrainer.last_layer_grad`."""
+where the two last-layer gradients come from `last_layer(d_image_term)` -- `FirstStageTrainer.last_layer_grad`.
+
+`LPIPSWithDiscriminator` is the same arrangement for `AutoencoderKL`: the pixel term is a sum under a learned-scale NLL
+(ldmk_l1_sum_grad), and the KL term enters at the bottleneck (`FirstStageTrainer.backward(kl_weight=...)`), not here."""
+import math
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -72,17 +78,7 @@ class VQLPIPSWithDiscriminator(nn.Module):
             raise ValueError(f"VQLPIPSWithDiscriminator: disc_loss={disc_loss!r}, pixel_loss={pixel_loss!r}")
         if use_actnorm or disc_conditional:
             raise NotImplementedError("VQLPIPSWithDiscriminator: use_actnorm / disc_conditional are not built")
-        if isinstance(perceptual_loss, dict) and "target" in perceptual_loss:      # a YAML lossconfig names the network
-            from .util import instantiate_from_config
-            perceptual_loss = instantiate_from_config(perceptual_loss)
-        if isinstance(perceptual_loss, nn.Module):
-            self.perceptual_loss = perceptual_loss.eval()
-        elif perceptual_weight > 0:
-            raise NotImplementedError("VQLPIPSWithDiscriminator: perceptual_weight > 0 needs a perceptual network, and the "
-                                      "pretrained LPIPS weights cannot be obtained offline: pass one as perceptual_loss=<module> "
-                                      "(inputs, reconstructions) -> (n,1,1,1), or set perceptual_weight=0")
-        else:
-            self.perceptual_loss = None
+        self.perceptual_loss = _perceptual_module("VQLPIPSWithDiscriminator", perceptual_loss, perceptual_weight)
         self.codebook_weight, self.pixel_weight, self.perceptual_weight = codebook_weight, pixelloss_weight, perceptual_weight
         self.pixel_loss = pixel_loss
         self.discriminator = NLayerDiscriminator(input_nc=disc_in_channels, n_layers=disc_num_layers, ndf=disc_ndf)
@@ -141,6 +137,110 @@ class VQLPIPSWithDiscriminator(nn.Module):
         if counts is not None:
             log[f"{split}/perplexity"], log[f"{split}/cluster_usage"] = perplexity_from_counts(counts)
         return loss, log
+
+
+def _perceptual_module(name, perceptual_loss, perceptual_weight):
+    """The injected perceptual network of both losses: a module, a `target` dict naming one, or nothing with weight 0."""
+    if isinstance(perceptual_loss, dict) and "target" in perceptual_loss:      # a YAML lossconfig names the network
+        from .util import instantiate_from_config
+        perceptual_loss = instantiate_from_config(perceptual_loss)
+    if isinstance(perceptual_loss, nn.Module):
+        return perceptual_loss.eval()
+    if perceptual_weight > 0:
+        raise NotImplementedError(f"{name}: perceptual_weight > 0 needs a perceptual network, and the "
+                                  "pretrained LPIPS weights cannot be obtained offline: pass one as perceptual_loss=<module> "
+                                  "(inputs, reconstructions) -> (n,1,1,1), or set perceptual_weight=0")
+    return None
+
+
+class LPIPSWithDiscriminator(nn.Module):
+    """contperceptual.py:7-110, the loss of AutoencoderKL.  With C*H*W the image size per sample and n the batch:
+        rec_sum  = sum|x - xrec| + perceptual_weight * C*H*W * sum_b p_b
+        nll      = rec_sum / (exp(logvar) * n) + logvar * C*H*W
+        kl_loss  = sum_b kl_b / n
+        loss     = nll + kl_weight * kl_loss + d_weight * disc_factor * g_loss
+        d_image  = d nll / d xrec + d_weight * disc_factor * d g_loss / d xrec          (the KL term has no image gradient)
+    `logvar` is an nn.Parameter stored under `loss.logvar`, as in the reference; no optimizer of the reference owns it
+    (autoencoder.py:386-395), so it never moves, and its gradient is NOT computed here.  The perceptual network is injected
+    (`perceptual_loss=<module>`), as for VQLPIPSWithDiscriminator."""
+
+    def __init__(self, disc_start, logvar_init=0.0, kl_weight=1.0, pixelloss_weight=1.0, disc_num_layers=3, disc_in_channels=3,
+                 disc_factor=1.0, disc_weight=1.0, perceptual_weight=1.0, use_actnorm=False, disc_conditional=False,
+                 disc_loss="hinge", perceptual_loss="lpips"):
+        super().__init__()
+        if disc_loss not in ("hinge", "vanilla"):
+            raise ValueError(f"LPIPSWithDiscriminator: disc_loss={disc_loss!r}")
+        if use_actnorm or disc_conditional:
+            raise NotImplementedError("LPIPSWithDiscriminator: use_actnorm / disc_conditional are not built")
+        self.perceptual_loss = _perceptual_module("LPIPSWithDiscriminator", perceptual_loss, perceptual_weight)
+        self.kl_weight, self.pixel_weight, self.perceptual_weight = kl_weight, pixelloss_weight, perceptual_weight
+        self.logvar = nn.Parameter(torch.ones(size=()) * logvar_init)
+        self.discriminator = NLayerDiscriminator(input_nc=disc_in_channels, n_layers=disc_num_layers)
+        self.discriminator_iter_start = disc_start
+        self.disc_loss = hinge_d_loss if disc_loss == "hinge" else vanilla_d_loss
+        self.disc_factor, self.discriminator_weight, self.disc_conditional = disc_factor, disc_weight, disc_conditional
+        self.d_image = None
+        self._lv = None
+
+    calculate_adaptive_weight = VQLPIPSWithDiscriminator.calculate_adaptive_weight
+
+    def _logvar_host(self):
+        """(logvar, exp(logvar)) as Python floats, read from the device again only when the parameter has changed."""
+        key = (self.logvar.data_ptr(), self.logvar._version)
+        if self._lv is None or self._lv[0] != key:
+            lv = float(self.logvar.detach())
+            self._lv = (key, lv, math.exp(lv))
+        return self._lv[1], self._lv[2]
+
+    def assemble(self, rec_sum, p_sum, kl, g_loss, d_weight, disc_factor, n, chw, split="train"):
+        """The host arithmetic of the generator step from its ingredients (tensors on any device): -> (loss, log) with the
+        reference's eight log entries (contperceptual.py:85-91)."""
+        lv = self.logvar.detach().to(rec_sum.device)
+        rec_total = rec_sum + self.perceptual_weight * chw * p_sum
+        nll = rec_total / (torch.exp(lv) * n) + lv * chw
+        kl_loss = kl.sum() / kl.shape[0]
+        loss = nll + self.kl_weight * kl_loss + d_weight * disc_factor * g_loss
+        log = {f"{split}/total_loss": loss.detach().mean(), f"{split}/logvar": self.logvar.detach(),
+               f"{split}/kl_loss": kl_loss.detach().mean(), f"{split}/nll_loss": nll.detach().mean(),
+               f"{split}/rec_loss": (rec_total / (n * chw)).detach().mean(), f"{split}/d_weight": d_weight.detach(),
+               f"{split}/disc_factor": torch.tensor(disc_factor), f"{split}/g_loss": g_loss.detach().mean()}
+        return loss, log
+
+    def forward(self, inputs, reconstructions, posteriors, optimizer_idx, global_step, last_layer=None, cond=None,
+                split="train", weights=None):
+        """The reference's signature.  `posteriors`: a DiagonalGaussianDistribution, or the per-sample KL (n,) the trainer's
+        forward kept.  optimizer_idx 0 -> (loss, log) and `self.d_image` for `FirstStageTrainer.backward`; `last_layer` is a
+        callable image gradient -> last-layer weight gradient (None: d_weight = 0).  optimizer_idx 1 -> (d_loss, log) with
+        autograd attached to the discriminator's parameters."""
+        if cond is not None or weights is not None:
+            raise NotImplementedError("LPIPSWithDiscriminator: cond (disc_conditional) and weights are not built")
+        x, xrec = inputs.contiguous().float(), reconstructions.detach().contiguous().float()
+        disc_factor = adopt_weight(self.disc_factor, global_step, threshold=self.discriminator_iter_start)
+        if optimizer_idx == 1:
+            logits_real, logits_fake = self.discriminator(x), self.discriminator(xrec)
+            d_loss = disc_factor * self.disc_loss(logits_real, logits_fake)
+            return d_loss, {f"{split}/disc_loss": d_loss.detach().mean(), f"{split}/logits_real": logits_real.detach().mean(),
+                            f"{split}/logits_fake": logits_fake.detach().mean()}
+        n, chw = x.shape[0], x[0].numel()
+        kl = posteriors if torch.is_tensor(posteriors) else posteriors.kl()
+        _, var = self._logvar_host()
+        scale = 1.0 / (var * n)                                     # d nll / d rec_sum
+        rec_sum, d_nll = T.l1_sum_grad(xrec, x, scale)
+        rec_sum, p_sum = rec_sum[0], torch.zeros((), device=x.device)
+        leaf = xrec.clone().requires_grad_(True)
+        with torch.enable_grad():
+            if self.perceptual_loss is not None and self.perceptual_weight > 0:
+                p = self.perceptual_loss(x, leaf).sum()
+                p_sum = p.detach()
+                d_nll = d_nll + (self.perceptual_weight * chw * scale) * torch.autograd.grad(p, leaf)[0]
+            g_loss = -self.discriminator(leaf).mean()
+            d_g = torch.autograd.grad(g_loss, leaf)[0]
+        if last_layer is not None and self.disc_factor > 0.0:
+            d_weight = self.calculate_adaptive_weight(last_layer(d_nll), last_layer(d_g))
+        else:
+            d_weight = torch.zeros((), device=x.device)
+        self.d_image = d_nll + (d_weight * disc_factor) * d_g
+        return self.assemble(rec_sum, p_sum, kl.to(x.device), g_loss.detach(), d_weight, disc_factor, n, chw, split)
 
 
 class StandInPerceptual(nn.Module):

@@ -39,6 +39,8 @@ KL_F8_SMALL = dict(embed_dim=4,
 VQ_TRAIN_SMALL = dict(embed_dim=3, n_embed=64,
                       ddconfig=dict(double_z=False, z_channels=3, resolution=32, in_channels=3, out_ch=3, ch=64, ch_mult=[1, 2],
                                     num_res_blocks=1, attn_resolutions=[16], dropout=0.0))
+# the KL sibling: the same trunk with a 6-channel moment head (z_channels = embed_dim = 3)
+KL_TRAIN_SMALL = dict(embed_dim=3, ddconfig=dict(VQ_TRAIN_SMALL["ddconfig"], double_z=True))
 SCHEDULE = dict(timesteps=1000, linear_start=0.0015, linear_end=0.0205)
 
 
@@ -138,6 +140,15 @@ def make_vq_first_stage(vq=None, seed=0, device="cuda"):
     vq = vq or VQ_TRAIN_SMALL
     m = VQModelInterface(embed_dim=vq["embed_dim"], n_embed=vq["n_embed"], ddconfig=dict(vq["ddconfig"]),
                          lossconfig=dict(target="torch.nn.Identity"))
+    load_recipe(m, seed=seed)
+    return m.to(device).eval()
+
+
+def make_kl_first_stage(kl=None, seed=0, device="cuda"):
+    """A stand-alone KL first stage with recipe weights (the KL kind of train_first_stage.FirstStageTrainer)."""
+    from .autoencoder import AutoencoderKL
+    kl = kl or KL_TRAIN_SMALL
+    m = AutoencoderKL(embed_dim=kl["embed_dim"], ddconfig=dict(kl["ddconfig"]), lossconfig=dict(target="torch.nn.Identity"))
     load_recipe(m, seed=seed)
     return m.to(device).eval()
 

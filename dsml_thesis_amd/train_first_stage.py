@@ -1,8 +1,9 @@
-"""Training the VQGAN first stage (ldm/models/autoencoder.py:14-262 VQModel).
+"""Training the VQGAN and KL first stages (ldm/models/autoencoder.py:14-262 VQModel, :285-423 AutoencoderKL).
 
-`FirstStageTrainer(vq)`: encoder -> quant_conv -> quantise -> post_quant_conv -> decoder as one tape with parameter
-gradients.  Parameters, gradients and Adam moments live in one `FlatParams` arena in the kernels' packed layouts, in forward
-order, like `UNetTrainer`.  The ResnetBlock / AttnBlock tapes below are a SECOND COPY of `DecoderGrad`'s (train_decoder.py),
+`FirstStageTrainer(model)`: encoder -> quant_conv -> bottleneck -> post_quant_conv -> decoder as one tape with parameter
+gradients.  The bottleneck is one of two kinds: the quantiser of a VQ model (`bottleneck == "vq"`), or the diagonal-Gaussian
+posterior of an `AutoencoderKL` with its KL term (`"kl"`, csrc/kl_train.hip); everything else is shared.
+Parameters, gradients and Adam moments live in one `FlatParams` arena in the kernels' packed layouts, in forward order, like `UNetTrainer`.  The ResnetBlock / AttnBlock tapes below are a SECOND COPY of `DecoderGrad`'s (train_decoder.py),
 written over arena views and with the weight gradients emitted instead of dropped (T.wgrad_conv3x3 / T.wgrad_linear, T.gn_bwd
 with dgamma / dbeta): `DecoderGrad` reads a frozen module's tensors and caches its data-gradient weights, which a trainer
 whose weights move every step cannot share, so the two are kept in step by hand.  The quantiser and the two narrow 1x1
@@ -34,9 +35,12 @@ class FirstStageTrainer:
         self.vq, self.sd = vq, vq._sd
         self.dev = next(vq.parameters()).device
         e, d = vq.encoder, vq.decoder
-        if max(e.in_channels, e.z_out, d.z_channels, d.out_ch) > 32 or e.ch % 32 or not hasattr(vq, "quantize"):
-            raise NotImplementedError("FirstStageTrainer: a VQ autoencoder with ch % 32 == 0 and boundary widths <= 32")
-        self.beta, self.legacy = float(vq.quantize.beta), bool(getattr(vq.quantize, "legacy", True))
+        from .autoencoder import AutoencoderKL
+        self.bottleneck = "vq" if hasattr(vq, "quantize") else ("kl" if isinstance(vq, AutoencoderKL) else None)
+        if max(e.in_channels, e.z_out, d.z_channels, d.out_ch) > 32 or e.ch % 32 or self.bottleneck is None:
+            raise NotImplementedError("FirstStageTrainer: a VQ or KL autoencoder with ch % 32 == 0 and boundary widths <= 32")
+        if self.bottleneck == "vq":
+            self.beta, self.legacy = float(vq.quantize.beta), bool(getattr(vq.quantize, "legacy", True))
         self.P = FlatParams()
         self.kind = {}          # arena name (= state-dict key) -> how its packed layout maps to the reference's
         self._collect()
@@ -103,7 +107,8 @@ class FirstStageTrainer:
         self._add_norm("encoder.norm_out")
         self._add_conv("encoder.conv_out", "conv_padout")
         self._add_conv("quant_conv", "c11")
-        self._add("quantize.embedding.weight", "raw")
+        if self.bottleneck == "vq":
+            self._add("quantize.embedding.weight", "raw")
         self._add_conv("post_quant_conv", "c11")
         self._add_conv("decoder.conv_in", "conv_padin")
         self._add_resnet("decoder.mid.block_1.", d.mid.block_1)
@@ -281,33 +286,9 @@ class FirstStageTrainer:
         out[..., :c] = x_nchw.permute(0, 2, 3, 1)
         return out
 
-    def forward(self, x):
-        """x (n,in_channels,H,W) -> xrec (n,out_ch,H,W); keeps z (pre-quantisation latent), zq, idx (int32) and qloss
-        (the unweighted codebook loss, a device scalar).  VQModel.forward, autoencoder.py:76-89,104-110."""
-        if not x.is_cuda:
-            raise L.LdmkError("FirstStageTrainer.forward: CUDA tensors only (no CPU fallback)")
-        T.set_compute("f32")
-        vq, e, d, p = self.vq, self.vq.encoder, self.vq.decoder, self.P.p
-        self.tape = []
-        n = x.shape[0]
-        h = self._plain(self._conv(self._pad_nhwc(x.float()), "encoder.conv_in", need_dx=False))
-        for lvl in range(e.num_resolutions):
-            dn = e.down[lvl]
-            for ib in range(e.num_res_blocks):
-                h = self._resnet(f"encoder.down.{lvl}.block.{ib}.", dn.block[ib], h)
-                if len(dn.attn) > 0:
-                    h = self._attn(f"encoder.down.{lvl}.attn.{ib}.", h)
-            if lvl != e.num_resolutions - 1:
-                h = self._plain(self._conv(h, f"encoder.down.{lvl}.downsample.conv", stride=2, pad_lo=0))
-        h = self._resnet("encoder.mid.block_1.", e.mid.block_1, h)
-        h = self._attn("encoder.mid.attn_1.", h)
-        h = self._resnet("encoder.mid.block_2.", e.mid.block_2, h)
-        _, lh, lw, cf = h.shape
-        y, b_no = self._gn(h, "encoder.norm_out", True)
-        hz_pad, b_co = self._conv(y.view(n, lh, lw, cf), "encoder.conv_out")
-        self.tape.append(lambda g: b_no(b_co(g).view(n * lh * lw, -1)))
-        zc, ed = e.z_out, vq.embed_dim
-        hz = hz_pad[..., :zc].permute(0, 3, 1, 2).contiguous()
+    def _quantise(self, hz):
+        """quant_conv -> nearest code (straight-through) -> post_quant_conv; pushes the backward of the three."""
+        p, d = self.P.p, self.vq.decoder
         z = ops.conv1x1_nchw(hz, p["quant_conv.weight"], p["quant_conv.bias"])
         cb = p["quantize.embedding.weight"]
         zq, idx = ops.vq_nearest(z, cb)
@@ -333,7 +314,64 @@ class FirstStageTrainer:
                                            accumulate=self.acc_params)
             return self._pad_nhwc(dhz)
         self.tape.append(bwd_quant)
+        return pq
 
+    def _gaussian(self, hz, noise, sample_posterior):
+        """quant_conv -> moments -> z = mean + std * noise (or the mean) and the per-sample KL -> post_quant_conv; pushes
+        the backward of the three (AutoencoderKL.encode / forward / decode, autoencoder.py:324-342)."""
+        p, d = self.P.p, self.vq.decoder
+        moments = ops.conv1x1_nchw(hz, p["quant_conv.weight"], p["quant_conv.bias"])
+        if sample_posterior:
+            shape = (moments.shape[0], moments.shape[1] // 2) + tuple(moments.shape[2:])
+            noise = self.vq.sample_noise(shape) if noise is None else noise
+            noise = noise.to(self.dev, torch.float32).contiguous()
+        else:
+            noise = None
+        z, kl = T.gauss_kl_fwd(moments, noise)
+        pq = ops.conv1x1_nchw(z, p["post_quant_conv.weight"], p["post_quant_conv.bias"])
+        self.moments, self.z, self.kl, self.noise = moments, z, kl, noise
+
+        def bwd_gauss(dpq_pad):
+            g = self.P.g
+            dpq = dpq_pad[..., :d.z_channels].permute(0, 3, 1, 2).contiguous()
+            dz, _, _ = T.conv1x1_nchw_bwd(z, dpq, p["post_quant_conv.weight"], dw=g["post_quant_conv.weight"],
+                                          db=g["post_quant_conv.bias"], accumulate=self.acc_params)
+            dmom = T.gauss_kl_bwd(moments, noise, dz, self._kl_weight / moments.shape[0])
+            dhz, _, _ = T.conv1x1_nchw_bwd(hz, dmom, p["quant_conv.weight"], dw=g["quant_conv.weight"], db=g["quant_conv.bias"],
+                                           accumulate=self.acc_params)
+            return self._pad_nhwc(dhz)
+        self.tape.append(bwd_gauss)
+        return pq
+
+    def forward(self, x, noise=None, sample_posterior=True):
+        """x (n,in_channels,H,W) -> xrec (n,out_ch,H,W).  VQ (VQModel.forward, autoencoder.py:76-89,104-110): keeps z
+        (pre-quantisation latent), zq, idx (int32) and qloss (the unweighted codebook loss, a device scalar).  KL
+        (AutoencoderKL.forward, autoencoder.py:335-342): keeps moments, z (the draw from `noise`, default
+        `model.sample_noise`; the mean without sample_posterior) and kl (n,); `noise` / `sample_posterior` are KL's alone."""
+        if not x.is_cuda:
+            raise L.LdmkError("FirstStageTrainer.forward: CUDA tensors only (no CPU fallback)")
+        T.set_compute("f32")
+        vq, e, d, p = self.vq, self.vq.encoder, self.vq.decoder, self.P.p
+        self.tape = []
+        n = x.shape[0]
+        h = self._plain(self._conv(self._pad_nhwc(x.float()), "encoder.conv_in", need_dx=False))
+        for lvl in range(e.num_resolutions):
+            dn = e.down[lvl]
+            for ib in range(e.num_res_blocks):
+                h = self._resnet(f"encoder.down.{lvl}.block.{ib}.", dn.block[ib], h)
+                if len(dn.attn) > 0:
+                    h = self._attn(f"encoder.down.{lvl}.attn.{ib}.", h)
+            if lvl != e.num_resolutions - 1:
+                h = self._plain(self._conv(h, f"encoder.down.{lvl}.downsample.conv", stride=2, pad_lo=0))
+        h = self._resnet("encoder.mid.block_1.", e.mid.block_1, h)
+        h = self._attn("encoder.mid.attn_1.", h)
+        h = self._resnet("encoder.mid.block_2.", e.mid.block_2, h)
+        _, lh, lw, cf = h.shape
+        y, b_no = self._gn(h, "encoder.norm_out", True)
+        hz_pad, b_co = self._conv(y.view(n, lh, lw, cf), "encoder.conv_out")
+        self.tape.append(lambda g: b_no(b_co(g).view(n * lh * lw, -1)))
+        hz = hz_pad[..., :e.z_out].permute(0, 3, 1, 2).contiguous()
+        pq = self._quantise(hz) if self.bottleneck == "vq" else self._gaussian(hz, noise, sample_posterior)
         h = self._plain(self._conv(self._pad_nhwc(pq), "decoder.conv_in"))
         h = self._resnet("decoder.mid.block_1.", d.mid.block_1, h)
         h = self._attn("decoder.mid.attn_1.", h)
@@ -353,11 +391,12 @@ class FirstStageTrainer:
         self.tape.append(lambda g: b_no2(b_co2(g).view(nf * hf * wf, -1)))
         return img_pad[..., :d.out_ch].permute(0, 3, 1, 2).contiguous()
 
-    def backward(self, d_image, codebook_weight=1.0):
-        """d_image (n,out_ch,H,W): gradient of the image-space loss terms; the codebook loss enters with `codebook_weight`.
-        Fills (with acc_params: adds to) P.grad; `counts` holds the hits per code afterwards."""
+    def backward(self, d_image, codebook_weight=1.0, kl_weight=1.0):
+        """d_image (n,out_ch,H,W): gradient of the image-space loss terms.  VQ: the codebook loss enters with
+        `codebook_weight`, and `counts` holds the hits per code afterwards.  KL: kl_weight * mean_b kl[b] enters at the
+        bottleneck.  Fills (with acc_params: adds to) P.grad."""
         T.set_compute("f32")
-        self._codebook_weight = float(codebook_weight)
+        self._codebook_weight, self._kl_weight = float(codebook_weight), float(kl_weight)
         g = self._pad_nhwc(d_image.float())
         for fn in reversed(self.tape):
             g = fn(g)

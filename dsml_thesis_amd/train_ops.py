@@ -368,6 +368,55 @@ def conv1x1_nchw_bwd(x, dy, w, dx=None, dw=None, db=None, accumulate=False, want
     return dx, dw, db
 
 
+def l1_sum_grad(pred, target, g, dpred=None, total=None):
+    """-> (sum|pred - target| [1], dpred = g * sign(pred - target)): the pixel term of the NLL loss, whose gradient scale
+    1 / (n exp(logvar)) is real-valued (l1_grad takes an integer denominator and returns the mean)."""
+    ops._chk(pred, "l1_sum_grad pred")
+    ops._chk(target, "l1_sum_grad target")
+    if target.numel() != pred.numel():
+        raise ValueError(f"l1_sum_grad: pred {tuple(pred.shape)} against target {tuple(target.shape)}")
+    dpred = torch.empty_like(pred) if dpred is None else dpred
+    total = _f32(1, device=pred.device) if total is None else total
+    scratch = torch.empty(256, device=pred.device, dtype=torch.float64)
+    L.call("ldmk_l1_sum_grad", _ptr(pred), _ptr(target), _ptr(dpred), pred.numel(), float(g), _ptr(total), _ptr(scratch), stream())
+    return total, dpred
+
+
+def _kl_dims(moments, what, **same):
+    ops._chk(moments, what)
+    if moments.dim() != 4 or moments.shape[1] % 2:
+        raise ValueError(f"{what}: moments must be (n, 2e, h, w), got {tuple(moments.shape)}")
+    n, c2, h, w_ = moments.shape
+    for name, t in same.items():
+        ops._chk(t, f"{what} {name}")
+        if t is not None and tuple(t.shape) != (n, c2 // 2, h, w_):
+            raise ValueError(f"{what}: {name} {tuple(t.shape)} against the mean {(n, c2 // 2, h, w_)}")
+    return n, c2 // 2, h * w_
+
+
+def gauss_kl_fwd(moments, noise=None, z=None, kl=None):
+    """The KL bottleneck: moments (n,2e,h,w) -> (z (n,e,h,w), kl (n,)).  z = mean + std * noise with the bits of
+    ops.gauss_posterior(moments, noise, z=True) (noise None: the mean), kl[b] = 0.5 sum(mean^2 + var - 1 - logvar)."""
+    n, e, hw = _kl_dims(moments, "gauss_kl_fwd", noise=noise, z=z)
+    z = _f32(n, e, *moments.shape[2:], device=moments.device) if z is None else z
+    kl = _f32(n, device=moments.device) if kl is None else kl
+    scratch = torch.empty(64 * n, device=moments.device, dtype=torch.float64)
+    L.call("ldmk_gauss_kl_fwd", _ptr(moments), _ptr(noise), _ptr(z), _ptr(kl), n, e, hw, _ptr(scratch), stream())
+    return z, kl
+
+
+def gauss_kl_bwd(moments, noise=None, dz=None, w=0.0, dmoments=None):
+    """Backward of gauss_kl_fwd for a loss <dz, z> + w * sum_b kl[b] -> dmoments (n,2e,h,w).  dz None: the KL term alone;
+    noise None (the mode was decoded): no std term.  The raw log-variance takes gradient on [-30, 20], bounds included."""
+    n, e, hw = _kl_dims(moments, "gauss_kl_bwd", noise=noise, dz=dz)
+    dmoments = torch.empty_like(moments) if dmoments is None else dmoments
+    if dmoments.shape != moments.shape:
+        raise ValueError(f"gauss_kl_bwd: dmoments {tuple(dmoments.shape)} against moments {tuple(moments.shape)}")
+    ops._chk(dmoments, "gauss_kl_bwd dmoments")
+    L.call("ldmk_gauss_kl_bwd", _ptr(moments), _ptr(noise), _ptr(dz), float(w), _ptr(dmoments), n, e, hw, stream())
+    return dmoments
+
+
 def adamw_(p, g, m, v, lr, betas, eps, weight_decay, step):
     L.call("ldmk_adamw", _ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), lr, betas[0], betas[1], eps, weight_decay, step, stream())
 

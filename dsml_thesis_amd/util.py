@@ -12,6 +12,8 @@ TARGET_MAP = {
     "ldm.modules.losses.vqperceptual.VQLPIPSWithDiscriminator": "dsml_thesis_amd.losses.VQLPIPSWithDiscriminator",
     "ldm.modules.losses.VQLPIPSWithDiscriminator": "dsml_thesis_amd.losses.VQLPIPSWithDiscriminator",
     "taming.modules.losses.vqperceptual.VQLPIPSWithDiscriminator": "dsml_thesis_amd.losses.VQLPIPSWithDiscriminator",
+    "ldm.modules.losses.contperceptual.LPIPSWithDiscriminator": "dsml_thesis_amd.losses.LPIPSWithDiscriminator",
+    "ldm.modules.losses.LPIPSWithDiscriminator": "dsml_thesis_amd.losses.LPIPSWithDiscriminator",
     "ldm.models.autoencoder.AutoencoderKL": "dsml_thesis_amd.autoencoder.AutoencoderKL",
     "ldm.models.autoencoder.IdentityFirstStage": "dsml_thesis_amd.autoencoder.IdentityFirstStage",
     "ldm.models.diffusion.ddpm.LatentDiffusion": "dsml_thesis_amd.ddpm.LatentDiffusion",

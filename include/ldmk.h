@@ -838,6 +838,23 @@ int ldmk_conv1x1_nchw_bwd(const float* x, const float* dy, const float* w, float
 int ldmk_l1_grad(const float* pred, const float* target, float* dpred, long long n, long long denom, float* loss,
                  double* scratch, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * First-stage (KL) training (csrc/kl_train.hip); the conventions of the VQGAN kernels above.
+ * The Gaussian bottleneck of AutoencoderKL over moments (n, 2e, hw) = [mean | raw log-variance], lv = clamp(raw, -30, 20):
+ *   z (n, e, hw) = mean + exp(0.5 lv) * noise  -- the bits of ldmk_gauss_posterior at scale 1; noise NULL: the mean
+ *   kl[b] = 0.5 sum_b (mean^2 + exp(lv) - 1 - lv)      (distributions.py:44-49)      scratch = 64 n doubles
+ * and its backward into dmoments (n, 2e, hw), for a loss  <dz, z> + w sum_b kl[b]:
+ *   d mean = dz + w mean;   d raw = 0.5 (dz noise exp(0.5 lv) + w (exp(lv) - 1)) where -30 <= raw <= 20, 0 elsewhere
+ * dz NULL: the KL term alone; noise NULL: no std term. */
+int ldmk_gauss_kl_fwd(const float* moments, const float* noise, float* z, float* kl, int n, int e, int hw, double* scratch,
+                      void* stream);
+int ldmk_gauss_kl_bwd(const float* moments, const float* noise, const float* dz, float w, float* dmoments, int n, int e, int hw,
+                      void* stream);
+/* sum = sum|pred-target| (not a mean), dpred = g sign(pred-target) with sign(0) = 0 and a NaN staying a NaN: the pixel term of
+ * the NLL loss, whose scale 1 / (n exp(logvar)) is no integer (contperceptual.py:48-58).  scratch = 256 doubles. */
+int ldmk_l1_sum_grad(const float* pred, const float* target, float* dpred, long long n, float g, float* sum, double* scratch,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif
