@@ -8,19 +8,18 @@ loop itself is MI355X-native: the latent, the timestep vector, the step counter 
 in device memory, one step = the UNet launch program + one fused update kernel, no host sync, and the step can
 be captured once in a hipGraph and replayed S times.  Additions over the reference: `noise=` (pre-generated
 per-step noise for eta>0 parity), `use_graph=`, `policy_batch=` (sharding-invariant tile choice) and
-`fixed_identity=` for progressive sampling.
+`fixed_identity=` for progressive sampling.  What this loop shares with the PLMS, DPM-Solver and DDPM loops -- the
+run preparation, the latent's two guidance halves, loop state on the program, graph capture, the option handling -- is
+sampling_loop.py; the step (`one_step`: its launches in order) and the host loop are here.
 """
-import types
-
 import numpy as np
 import torch
 
 from . import lib as L
+from . import sampling_loop as SL
 from . import schedule as S_
-from .engine import GraphedProgram
+from .sampling_loop import C12, C34  # noqa: F401  (the talking-face dict keys, imported from here by scripts)
 from .unet import rerun_if_flags_tripped
-
-C12, C34 = "class_label_&_audio", "motion_&_id"
 
 
 class DDIMSampler(object):
@@ -81,97 +80,17 @@ class DDIMSampler(object):
         tab, ts, _ = self._tables[key]
         return tab, ts, np.arange(self.ddpm_num_timesteps)
 
-    # ------------------------------------------------------------------------------------------
+    # ------------------------------------------------------------------------------------------ sampling_loop.py, on this model
     def _is_adm(self):
-        return getattr(self.model.model, "conditioning_key", None) == "adm"
+        return SL.is_adm(self.model)
 
-    @staticmethod
-    def _labels(cond):
-        """conditioning_key 'adm': the class-label vector y (B,) out of whatever form apply_model accepts (ddpm.py:893-994 wraps a
-        tensor as c_crossattn = [y]; DiffusionWrapper takes c_crossattn[0], :1417-1419)."""
-        if isinstance(cond, dict):
-            cond = cond.get("c_crossattn")
-        if isinstance(cond, (list, tuple)):
-            cond = cond[0]
-        return cond
+    _labels = staticmethod(SL.labels)
 
     def _split_cond(self, cond):
-        """-> (crossattn context (B,L,D), c_concat (B,C,H,W) or None); 'adm': (class labels (B,), None)."""
-        if self._is_adm():
-            return self._labels(cond), None
-        if isinstance(cond, dict):
-            if C12 in cond:                      # TF sampler conditioning, ddim2cond.py:165
-                return cond[C12], cond[C34]
-            cc = cond.get("c_crossattn")
-            ct = cond.get("c_concat")
-            cc = torch.cat(cc, 1) if isinstance(cc, (list, tuple)) else cc
-            ct = torch.cat(ct, 1) if isinstance(ct, (list, tuple)) else ct
-            return cc, ct
-        if isinstance(cond, (list, tuple)):
-            cond = torch.cat(list(cond), 1)
-        if cond is not None and getattr(self.model.model, "conditioning_key", None) == "concat":
-            return None, cond                    # DiffusionWrapper 'concat': the conditioning is the channel concat (ddpm.py:1407-1409)
-        return cond, None
+        return SL.split_cond(self.model, cond)
 
-    def _prepare_run(self, cond, shape, x_T, unconditional_guidance_scale, unconditional_conditioning, policy_batch, loops_name,
-                     float_time=False):
-        """What every sampling loop of this class does before its first step: start noise, conditioning split, guidance
-        doubling, 'adm' labels, the launch program (or the patch-wise evaluator) with its conditioning written and its context
-        program run, and the per-program dict `loops` that holds loop state under `loops_name` (one name per kind of loop, so the
-        loops never meet each other's state).  `float_time`: the program whose timestep input is the fp32 `t_f32`."""
-        dev = self.model.device
-        unet = self.model.model.diffusion_model
-        b = shape[0]
-        img0 = torch.randn(shape, device=dev) if x_T is None else x_T.to(dev, torch.float32)
-        ctx, cat = self._split_cond(cond)
-        cfg = not (unconditional_conditioning is None or unconditional_guidance_scale == 1.)
-        nb = 2 * b if cfg else b
-        y_in = None
-        if self._is_adm():
-            # class-conditional model (ddpm.py:1417-1419): the conditioning is the label vector y, which reaches the UNet as rows of
-            # its label embedding added to the timestep embedding -- constant over the run, written once into the program's
-            # `y_emb` input; guidance doubles it as [uncond | cond] like any conditioning (ddim.py:175)
-            y_in = ctx if not cfg else torch.cat([self._split_cond(unconditional_conditioning)[0], ctx])
-            assert y_in is not None and y_in.dim() == 1 and cat is None, "conditioning_key 'adm': conditioning = class labels (B,)"
-            ctx_in, cat_in = None, None
-        elif cfg:
-            uc, ucat = self._split_cond(unconditional_conditioning)
-            if ctx is None:                                # 'concat' conditioning: the guidance halves differ in the concat tensor
-                ctx_in, cat_in = None, torch.cat([ucat, cat])
-            else:
-                ctx_in = torch.cat([uc, ctx])              # ddim.py:175: [uncond | cond]
-                cat_in = None if cat is None else torch.cat([cat] * 2)
-        else:
-            ctx_in, cat_in = ctx, cat
-        ncat = 0 if cat_in is None else cat_in.shape[1]
-        L_ctx = 0 if ctx_in is None else ctx_in.shape[1]          # 0: unconditional UNet (no cross-attention)
-        policy_nb = None if policy_batch is None else (2 * policy_batch if cfg else policy_batch)
-        y_emb = None if y_in is None else unet.label_emb.weight.detach().float()[y_in.to(dev, torch.int64)]
-        if hasattr(self.model, "split_input_params"):
-            # patch-wise (ddpm.py:904-986): the latent lives in a full-size buffer of nb items ([uncond | cond] under guidance, so
-            # ldmk_ddim_step's contract holds); one step = unfold -> the program at batch L*nb -> fold -> the update on the
-            # full-size tensors.  Context / concat crops are written once per run.
-            pe = self.model._patched_eval(nb, shape[1], shape[2], shape[3], L_ctx, ncat, policy_batch=policy_nb, float_time=float_time)
-            pg = pe.pg
-            pe.set_cond(ctx_in, cat_in, y_emb)
-            x_buf, eps, run_net = pe.x, pe.eps, pe.run
-            loops = pe.loops.setdefault(loops_name, {})    # (never the plain loop's state of the same program)
-        else:
-            unet.policy_batch = policy_nb
-            pg = unet.program(nb, shape[2], shape[3], L_ctx, ncat, float_time=float_time)
-            x_buf, eps, run_net = pg.inputs["x"], pg.outputs["eps"], pg.run
-            if L_ctx:
-                pg.inputs["context"].copy_(ctx_in.reshape(nb * L_ctx, -1))
-            if ncat:
-                pg.inputs["c_concat"].copy_(cat_in)
-            if y_emb is not None:
-                pg.inputs["y_emb"].copy_(y_emb)
-            pg.ctx_program.run()                           # context-only projections: once per sample() call
-            # loop state (buffers, the captured step) lives ON the launch program it was captured over and dies with it: when the
-            # model drops its programs (a re-pack, an arithmetic fall-back) nothing keeps the old workspace or its hipGraph alive,
-            # and a new program can never be handed buffers of another batch size (rounds 2-4 keyed a sampler-side cache by id(pg))
-            loops = pg.__dict__.setdefault(f"_{loops_name}_loops", {})
-        return types.SimpleNamespace(dev=dev, b=b, img0=img0, cfg=cfg, pg=pg, x_buf=x_buf, eps=eps, run_net=run_net, loops=loops)
+    def _prepare_run(self, *args, **kwargs):
+        return SL.prepare_run(self.model, *args, **kwargs)
 
     @torch.no_grad()
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None,
@@ -179,14 +98,10 @@ class DDIMSampler(object):
                noise_dropout=0., score_corrector=None, corrector_kwargs=None, verbose=True, x_T=None,
                log_every_t=100, unconditional_guidance_scale=1., unconditional_conditioning=None,
                noise=None, use_graph=False, policy_batch=None, **kwargs):
-        if conditioning is None and getattr(self.model.model, "conditioning_key", "crossattn") is not None:
-            raise L.LdmkError("DDIMSampler.sample: conditioning is required (this model is cross-attention / concat "
+        SL.check_conditioning(self.model, conditioning, batch_size,
+                              "DDIMSampler.sample: conditioning is required (this model is cross-attention / concat "
                               "conditioned; the reference asserts the same in ddim2cond.py:80).  Only an unconditional LDM "
                               "(cond_stage_config '__is_unconditional__') samples with conditioning=None (ddim.py:77-84)")
-        ctx, cat0 = self._split_cond(conditioning)
-        first = ctx if ctx is not None else cat0
-        if first is not None and first.shape[0] != batch_size:
-            print(f"Warning: Got {first.shape[0]} conditionings but batch-size is {batch_size}")
         self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
         C_, H, W_ = shape
         size = (batch_size, C_, H, W_)
@@ -219,21 +134,13 @@ class DDIMSampler(object):
           score_corrector    `modify_score(model, e_t, x, t, c, **corrector_kwargs)` between the UNet and the update (:179-181);
                              a host callback, so it runs with eager launches."""
         r = self._prepare_run(cond, shape, x_T, unconditional_guidance_scale, unconditional_conditioning, policy_batch, "ddim")
-        dev, b, img0, cfg, pg, x_buf, eps, run_net, loops = r.dev, r.b, r.img0, r.cfg, r.pg, r.x_buf, r.eps, r.run_net, r.loops
+        dev, b, img0, pg, img, run_net = r.dev, r.b, r.img0, r.pg, r.img, r.run_net
         S = self.ddim_timesteps.shape[0]
         lib = pg.lib
-        n_ts = pg.inputs["t"].numel()                      # (patch-wise: L*nb entries, all the current timestep)
-        img = x_buf[:b]                                    # the latent lives in the UNet's input buffer (patch-wise: the full-size one)
-        img.copy_(img0)
-        if cfg:
-            x_buf[b:].copy_(img0)
+        t_buf = pg.inputs["t"]
+        n_ts = t_buf.numel()                               # (patch-wise: L*nb entries, all the current timestep)
         need_noise = self._eta != 0. or noise is not None
-        if mask is not None:
-            assert x0 is not None, "mask needs x0 (ddim.py:144)"
-            mask = mask.to(dev, torch.float32).expand(shape).contiguous()
-            x0 = x0.to(dev, torch.float32)
         if score_corrector is not None:
-            assert self.model.parameterization == "eps"
             use_graph = False                              # a host callback sits inside the step
         extras = mask is not None or quantize_denoised or score_corrector is not None or noise_dropout > 0. or temperature != 1.
         table, ts_table, tsteps = (self._inv_table if invert else self._table), self._ts_table, self.ddim_timesteps
@@ -250,38 +157,26 @@ class DDIMSampler(object):
             assert not invert and timesteps is None
             n_run = int(n_steps)
         assert 0 < n_run <= S, (n_run, S)
-        lkey = (cfg, float(unconditional_guidance_scale), self._sched_key, need_noise, bool(use_graph), noise is None, bool(invert),
-                bool(ddim_use_original_steps), n_run)
-        st = None if extras else loops.get(lkey)           # (option runs capture their own tensors: never cached)
-        if st is None:
-            st = dict(pred_x0=torch.empty_like(img0), step_idx=torch.zeros(1, dtype=torch.int32, device=dev),
-                      nz=torch.empty_like(img0) if need_noise else None, graph=None)
-            if not extras:
-                loops[lkey] = st
+        scale = float(unconditional_guidance_scale)
+        lkey = (r.cfg, scale, self._sched_key, need_noise, bool(use_graph), noise is None, bool(invert), bool(ddim_use_original_steps),
+                n_run)
+        st = r.state(lkey, lambda: dict(pred_x0=torch.empty_like(img0), step_idx=torch.zeros(1, dtype=torch.int32, device=dev),
+                                        nz=torch.empty_like(img0) if need_noise else None), cached=not extras)
         pred_x0, step_idx, nz_buf = st["pred_x0"], st["step_idx"], st["nz"]
         per = img0[0].numel()
-        scale = float(unconditional_guidance_scale)
         first = 0 if invert else n_run - 1
         adv = -1 if invert else 1
+        blend = SL.MaskBlend(r, self.model, mask, x0, mask_noise) if mask is not None else None
+        score = SL.score_source(r, self.model, score_corrector, corrector_kwargs, cond, scale, t_buf)
 
         def reset_state():
-            img.copy_(img0)
-            if cfg:
-                x_buf[b:].copy_(img0)
+            r.seed()
             step_idx.fill_(first)
-            pg.inputs["t"].fill_(int(tsteps[first]))
-
-        mnz = torch.zeros_like(img0) if mask is not None else None      # (zeros: the graph warm-up steps run before the first fill)
-        sqrt_ac, sqrt_1mac = self.model.sqrt_alphas_cumprod, self.model.sqrt_one_minus_alphas_cumprod
-        eps_c = torch.empty_like(img0) if score_corrector is not None else None
+            t_buf.fill_(int(tsteps[first]))
 
         def one_step():
-            if mask is not None:                           # ddim.py:143-146, timestep read from the device-side vector
-                tcur = pg.inputs["t"][:b]
-                img_orig = (sqrt_ac.gather(-1, tcur).view(b, 1, 1, 1) * x0 + sqrt_1mac.gather(-1, tcur).view(b, 1, 1, 1) * mnz)
-                img.copy_(img_orig * mask + (1. - mask) * img)
-                if cfg:
-                    x_buf[b:].copy_(img)
+            if blend is not None:
+                blend.blend(t_buf)
             if nz_buf is not None and (temperature != 1. or noise_dropout > 0.):
                 if temperature != 1.:
                     nz_buf.mul_(temperature)
@@ -289,60 +184,38 @@ class DDIMSampler(object):
                     nz_buf.copy_(torch.nn.functional.dropout(nz_buf, p=noise_dropout))
             a_prev = table[step_idx.long(), 1] if quantize_denoised else None      # read before the kernel advances the counter
             run_net()
-            e_ptr, k_cfg = eps.data_ptr(), (1 if cfg else 0)
-            if score_corrector is not None:                # ddim.py:179-181 acts on the guidance-combined score
-                e_t = eps[:b] if not cfg else eps[:b] + scale * (eps[b:] - eps[:b])
-                tcur = pg.inputs["t"][:b].clone()
-                eps_c.copy_(score_corrector.modify_score(self.model, e_t, img.clone(), tcur, cond, **(corrector_kwargs or {})))
-                e_ptr, k_cfg = eps_c.data_ptr(), 0
+            e_ptr, k_cfg = score()
             rc = lib.ldmk_ddim_step(img.data_ptr(), e_ptr, 0 if nz_buf is None else nz_buf.data_ptr(),
                                     table.data_ptr(), step_idx.data_ptr(), scale, k_cfg, img.data_ptr(),
-                                    pred_x0.data_ptr(), per, b, ts_table.data_ptr(), pg.inputs["t"].data_ptr(), n_ts, adv, S,
+                                    pred_x0.data_ptr(), per, b, ts_table.data_ptr(), t_buf.data_ptr(), n_ts, adv, S,
                                     torch.cuda.current_stream().cuda_stream)
             L.check(rc, "ldmk_ddim_step")
-            if quantize_denoised:                          # x_prev = sqrt(a_prev) Q(pred_x0) + dir_xt + noise (ddim.py:194-202)
-                q = self.model._quantize_denoised(pred_x0)
-                img.add_(torch.sqrt(a_prev) * (q - pred_x0))
-                pred_x0.copy_(q)
-            if cfg:
-                x_buf[b:].copy_(img)                       # both CFG halves see the same latent (ddim.py:173)
+            if quantize_denoised:
+                SL.quantize_fixup(self.model, img, pred_x0, a_prev)
+            r.share_latent()
+
+        def draw():                                        # the noise no list gives: eager, before step(); graphed, inside the capture
+            if nz_buf is not None and noise is None:
+                nz_buf.normal_()
+            if blend is not None:
+                blend.draw()
 
         reset_state()
-        step = one_step
-        if use_graph:
-            if st["graph"] is None:
-                if (nz_buf is not None and noise is None) or (mask is not None and mask_noise is None):
-                    def step_with_noise():
-                        if nz_buf is not None and noise is None:
-                            nz_buf.normal_()
-                        if mask is not None and mask_noise is None:
-                            mnz.normal_()
-                        one_step()
-                    st["graph"] = GraphedProgram(step_with_noise)
-                else:
-                    st["graph"] = GraphedProgram(one_step)
-                reset_state()                              # warm-up + capture advanced the device state
-            step = st["graph"].replay
-
+        step = r.stepper(st, one_step, reset_state, use_graph, draw)
         intermediates = {"x_inter": [img0], "pred_x0": [img0]}
         for i in range(n_run):
-            index = n_run - i - 1
-            if nz_buf is not None:
-                if noise is not None:
-                    nz_buf.copy_(noise[i])
-                elif not use_graph:
-                    nz_buf.normal_()
-            if mask is not None:
-                if mask_noise is not None:
-                    mnz.copy_(mask_noise[i])
-                elif not use_graph:
-                    mnz.normal_()
+            if noise is not None:
+                nz_buf.copy_(noise[i])
+            if blend is not None:
+                blend.feed(i)
+            if not use_graph:
+                draw()
             step()
             if callback:
                 callback(i)
             if img_callback:
                 img_callback(pred_x0, i)
-            if index % log_every_t == 0 or index == n_run - 1:
+            if SL.log_step(n_run - i - 1, log_every_t, n_run):
                 intermediates["x_inter"].append(img.clone())
                 intermediates["pred_x0"].append(pred_x0.clone())
         out = img.clone()
@@ -394,9 +267,7 @@ class DDIMSampler(object):
                x_prev.data_ptr(), pred_x0.data_ptr(), x[0].numel(), b, 0, 0, 0, 0, 0,
                torch.cuda.current_stream().cuda_stream)
         if quantize_denoised:                                # ddim.py:195-196
-            q = self.model._quantize_denoised(pred_x0)
-            x_prev = x_prev + torch.sqrt(table[int(index), 1]) * (q - pred_x0)
-            pred_x0 = q
+            SL.quantize_fixup(self.model, x_prev, pred_x0, table[int(index), 1])
         return x_prev, pred_x0
 
     # ------------------------------------------------------------------------------------------ img2img (SDEdit) pair
@@ -505,20 +376,10 @@ class DDIMSampler(object):
             assert not fixed_identity, "fixed-identity frames are independent already: one batched sample() call"
             return self._progressive_clips(int(clips), c1, xid, xmasks, audio_feats, S, shape, audio_window, eta, x_T,
                                            use_graph, policy_batch), None
-        m = self.model
-        if audio_feats.dim() == 3:
-            assert audio_feats.shape[0] == 1
-            audio_feats = audio_feats.squeeze(0)
-        T = audio_feats.shape[0]
+        c12_all, c3_all, T = self._clip_cond(c1, xmasks, audio_feats, audio_window)
         C_, H, W_ = shape
-        dev = m.device
-        idx = torch.tensor([[min(max(f + i, 0), T - 1) for i in range(-audio_window, audio_window + 1)]
-                            for f in range(T)], device=audio_feats.device)
-        c2_all = m.cond_stage_model_2(audio_feats[idx])                       # (T,1,768): one batched call
-        c12_all = torch.cat([c1.expand(T, -1, -1), c2_all], dim=2)            # (T,1,1024)
-        c3_all = m.encode_first_stage(xmasks)                                  # (T,c,h,w): one batched encode
         if x_T is None:
-            x_T = torch.randn(T, batch_size, C_, H, W_, device=dev)
+            x_T = torch.randn(T, batch_size, C_, H, W_, device=self.model.device)
         if fixed_identity:
             c34 = torch.cat([c3_all, xid.expand(T, -1, -1, -1)], dim=1)
             out, _ = self.sample(S, T, shape, {C12: c12_all, C34: c34}, eta=eta, x_T=x_T[:, 0], verbose=False,
@@ -534,6 +395,20 @@ class DDIMSampler(object):
             zid = img.clone()
         return frames, None
 
+    def _clip_cond(self, c1, xmasks, audio_feats, audio_window):
+        """One clip's conditioning over its T frames (progressive_sampling_difftalk.py:287-295) -> (c12 (T,1,1024), c3 (T,c,h,w), T):
+        the audio window around every frame, clamped to the clip, through cond_stage_model_2 in one batched call, next to the
+        identity-class embedding `c1` (1,1,D); and the masked frames through one batched first-stage encode."""
+        m = self.model
+        if audio_feats.dim() == 3:
+            assert audio_feats.shape[0] == 1
+            audio_feats = audio_feats.squeeze(0)
+        T = audio_feats.shape[0]
+        idx = torch.tensor([[min(max(f + i, 0), T - 1) for i in range(-audio_window, audio_window + 1)]
+                            for f in range(T)], device=audio_feats.device)
+        c2_all = m.cond_stage_model_2(audio_feats[idx])                       # (T,1,768)
+        return torch.cat([c1.expand(T, -1, -1), c2_all], dim=2), m.encode_first_stage(xmasks), T
+
     @torch.no_grad()
     def _progressive_clips(self, V, c1, xid, xmasks, audio_feats, S, shape, audio_window, eta, x_T, use_graph, policy_batch):
         """V independent talking-face videos, each the reference's serial chain (frame k+1's identity latent = frame k's
@@ -548,19 +423,8 @@ class DDIMSampler(object):
         C_, H, W_ = shape
         dev = m.device
         pol = V if policy_batch is None else policy_batch
-        c12, c3, Ts = [], [], []
-        for v in range(V):                                   # per-clip conditioning, exactly the single-clip calls
-            af = audio_feats[v]
-            if af.dim() == 3:
-                assert af.shape[0] == 1
-                af = af.squeeze(0)
-            T = af.shape[0]
-            idx = torch.tensor([[min(max(f + i, 0), T - 1) for i in range(-audio_window, audio_window + 1)]
-                                for f in range(T)], device=af.device)
-            c2_all = m.cond_stage_model_2(af[idx])
-            c12.append(torch.cat([c1[v:v + 1].expand(T, -1, -1), c2_all], dim=2))
-            c3.append(m.encode_first_stage(xmasks[v]))
-            Ts.append(T)
+        # per-clip conditioning, exactly the single-clip calls
+        c12, c3, Ts = zip(*[self._clip_cond(c1[v:v + 1], xmasks[v], audio_feats[v], audio_window) for v in range(V)])
         if x_T is None:
             x_T = [torch.randn(T, 1, C_, H, W_, device=dev) for T in Ts]
         zid = [xid[v:v + 1].clone() for v in range(V)]

@@ -16,6 +16,7 @@ import torch
 import torch.nn as nn
 
 from . import lib as L
+from . import sampling_loop as SL
 from . import schedule as S_
 from .distributions import DiagonalGaussianDistribution
 from .unet import rerun_if_flags_tripped
@@ -517,8 +518,9 @@ class LatentDiffusion(_Base):
         """ddpm.py:1167-1216.  Device-resident loop: the latent lives in the UNet program's input buffer, the
         per-sample timestep vector is rewritten by a kernel, one step = UNet program + fused posterior update, and
         (use_graph=True) the step is captured once in a hipGraph and replayed T times.
-        `noise`: optional per-step noise list (parity with a seeded reference run)."""
-        from .engine import GraphedProgram
+        `noise`: optional per-step noise list (parity with a seeded reference run).
+        The run is prepared by `sampling_loop.prepare_run`, as the DDIM, PLMS and DPM-Solver loops are, so `cond` takes every form
+        they take: what `apply_model` accepts, and the talking-face dict keys (`class_label_&_audio`, `motion_&_id`) besides."""
         log_every_t = log_every_t or self.log_every_t
         dev = self.betas.device
         b = shape[0]
@@ -547,59 +549,19 @@ class LatentDiffusion(_Base):
                 if img_callback:
                     img_callback(img, i)
             return (img, intermediates) if return_intermediates else img
-        if self.model.conditioning_key == "adm":          # labels in any form apply_model accepts: y, [y], {"c_crossattn": [y]}
-            ctx = cond.get("c_crossattn") if isinstance(cond, dict) else cond
-            ctx, cat = (ctx[0] if isinstance(ctx, (list, tuple)) else ctx), None
-        elif isinstance(cond, dict):
-            ctx = cond.get("c_crossattn")
-            cat = cond.get("c_concat")
-            ctx = torch.cat(ctx, 1) if isinstance(ctx, (list, tuple)) else ctx
-            cat = torch.cat(cat, 1) if isinstance(cat, (list, tuple)) else cat
-        elif self.model.conditioning_key == "concat":
-            ctx, cat = None, (torch.cat(cond, 1) if isinstance(cond, (list, tuple)) else cond)
-        else:
-            ctx, cat = (torch.cat(cond, 1) if isinstance(cond, (list, tuple)) else cond), None      # (None: unconditional)
-        unet = self.model.diffusion_model
-        y = None
-        if self.model.conditioning_key == "adm":          # class labels: rows of the label embedding, constant over the run (ddpm.py:1417-1419)
-            y, ctx = ctx, None
-            assert y is not None and y.dim() == 1 and cat is None, "conditioning_key 'adm': cond = class labels (B,)"
-        ncat = 0 if cat is None else cat.shape[1]
-        L_ctx = 0 if ctx is None else ctx.shape[1]
-        y_emb = None if y is None else unet.label_emb.weight.detach().float()[y.to(dev, torch.int64)]
-        if hasattr(self, "split_input_params"):
-            # patch-wise (ddpm.py:904-986): the latent lives in a full-size buffer; one step = unfold -> the program at batch
-            # L*b -> fold -> the posterior update on the full-size tensors.  Conditioning crops are written once per run.
-            pe = self._patched_eval(b, shape[1], shape[2], shape[3], L_ctx, ncat)
-            pg = pe.pg
-            pe.set_cond(ctx, cat, y_emb)
-            x_buf, eps, run_net = pe.x, pe.eps, pe.run
-            loops = pe.loops.setdefault("ddpm", {})             # (never the plain loop's state of the same program)
-        else:
-            pg = unet.program(b, shape[2], shape[3], L_ctx, ncat)
-            if L_ctx:
-                pg.inputs["context"].copy_(ctx.reshape(b * L_ctx, -1))
-            if ncat:
-                pg.inputs["c_concat"].copy_(cat)
-            if y_emb is not None:
-                pg.inputs["y_emb"].copy_(y_emb)
-            pg.ctx_program.run()
-            x_buf, eps, run_net = pg.inputs["x"], pg.outputs["eps"], pg.run
-            loops = pg.__dict__.setdefault("_ddpm_loops", {})   # (the state lives on the program and dies with it, like ddim.py's)
-        t_buf = pg.inputs["t"]                                  # (patch-wise: L*b entries, all the current timestep)
+        # no guidance in this loop, and `unet.policy_batch` stays what it is ("keep")
+        r = SL.prepare_run(self, cond, shape, img0, 1., None, "keep", "ddpm")
+        dev, x_buf, eps, run_net, lib = r.dev, r.img, r.eps, r.run_net, r.pg.lib       # (no second guidance half: img is all of x)
+        t_buf = r.pg.inputs["t"]                                # (patch-wise: L*b entries, all the current timestep)
         tab, logvar = self._ddpm_device_tables()
-        key = (timesteps, bool(use_graph), noise is None)
-        st = loops.get(key)
-        if st is None:
-            st = dict(nz=torch.empty_like(img0), idx=torch.zeros(1, dtype=torch.int32, device=dev),
-                      tt=torch.arange(self.num_timesteps, dtype=torch.int64, device=dev), graph=None)
-            loops[key] = st
+        st = r.state((timesteps, bool(use_graph), noise is None), lambda: dict(
+            nz=torch.empty_like(img0), idx=torch.zeros(1, dtype=torch.int32, device=dev),
+            tt=torch.arange(self.num_timesteps, dtype=torch.int64, device=dev)))
         nz, idx, tt = st["nz"], st["idx"], st["tt"]
         per = img0[0].numel()
-        lib = pg.lib
 
         def reset():
-            x_buf.copy_(img0)
+            r.seed()
             idx.fill_(timesteps - 1)
             t_buf.fill_(timesteps - 1)
 
@@ -614,20 +576,16 @@ class LatentDiffusion(_Base):
                                               stream), "ldmk_advance_timestep")
 
         reset()
-        step = one_step
-        if noise is not None:
+        if noise is not None:                                   # a given noise list wins over use_graph
             step = lambda: one_step(draw=False)
-        elif use_graph:
-            if st["graph"] is None:
-                st["graph"] = GraphedProgram(one_step)
-                reset()
-            step = st["graph"].replay
+        else:
+            step = r.stepper(st, one_step, reset, use_graph)
         intermediates = [img0]
         for k, i in enumerate(reversed(range(0, timesteps))):
             if noise is not None:
                 nz.copy_(noise[k])
             step()
-            if i % log_every_t == 0 or i == timesteps - 1:
+            if SL.log_step(i, log_every_t, timesteps):
                 intermediates.append(x_buf.clone())
             if callback:
                 callback(i)

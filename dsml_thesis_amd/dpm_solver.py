@@ -7,8 +7,8 @@ What is built is the branch the reference's sampler takes: the multistep DPM-Sol
 works in continuous time t in [1/N, 1] and evaluates the UNet at the REAL-valued model time (t - 1/N) 1000, so the loop runs over
 the float-time launch program (`UNetModel.program(..., float_time=True)`).  It evaluates the model once per step, the first step
 included, so every step is the same sequence -- UNet program, `ldmk_dpm_step`, advance -- and a whole run is S replays of one
-captured graph.  Everything before the first step is `DDIMSampler._prepare_run`, so every conditioning_key and
-`split_input_params` work as under DDIM.
+captured graph.  Everything before the first step is `sampling_loop.prepare_run` (through `DDIMSampler._prepare_run`), so every
+conditioning_key and `split_input_params` work as under DDIM; loop state and graph capture are that module's `Run`.
 
 The scalars of a run -- time steps, lambda, alpha, sigma, the per-step coefficients -- are one host table (`step_table`), computed in
 torch float32 on the CPU with the reference's operations in the reference's order: h is a difference of two lambda of magnitude ~5,
@@ -23,7 +23,6 @@ import torch
 
 from . import lib as L
 from .ddim import DDIMSampler
-from .engine import GraphedProgram
 from .unet import rerun_if_flags_tripped
 
 ROW = 12            # floats per table row (include/ldmk.h, ldmk_dpm_step)
@@ -194,27 +193,22 @@ class DPMSolverSampler(DDIMSampler):
                   unconditional_conditioning, use_graph, policy_batch, want_inter):
         r = self._prepare_run(cond, shape, x_T, unconditional_guidance_scale, unconditional_conditioning, policy_batch, "dpm",
                               float_time=True)
-        dev, b, img0, cfg, pg, x_buf, eps, run_net, loops = r.dev, r.b, r.img0, r.cfg, r.pg, r.x_buf, r.eps, r.run_net, r.loops
+        dev, b, img0, cfg, pg, img, eps, run_net = r.dev, r.b, r.img0, r.cfg, r.pg, r.img, r.eps, r.run_net
         tab = self._table_for(S, order, skip_type, lower_order_final)
         table, t_first, max_order = tab.device_table, float(tab.t_input[0]), max(tab.orders)
         lib = pg.lib
         t_buf = pg.inputs["t_f32"]
         n_ts = t_buf.numel()                               # (patch-wise: L*nb entries, all the current model time)
-        img = x_buf[:b]                                    # the latent lives in the UNet's input buffer, as in the DDIM loop
         scale = float(unconditional_guidance_scale)
-        lkey = (cfg, scale, tab.key, bool(use_graph))
-        st = loops.get(lkey)
-        if st is None:
-            # ring[k % 3] = the data prediction of step k (ldmk_dpm_step); step_idx = the current step
-            st = loops[lkey] = dict(pred_x0=torch.empty_like(img0), ring=torch.empty((3,) + tuple(img0.shape), device=dev),
-                                    step_idx=torch.zeros(1, dtype=torch.int32, device=dev), graph=None)
+        # ring[k % 3] = the data prediction of step k (ldmk_dpm_step); step_idx = the current step
+        st = r.state((cfg, scale, tab.key, bool(use_graph)), lambda: dict(
+            pred_x0=torch.empty_like(img0), ring=torch.empty((3,) + tuple(img0.shape), device=dev),
+            step_idx=torch.zeros(1, dtype=torch.int32, device=dev)))
         pred_x0, ring, step_idx = st["pred_x0"], st["ring"], st["step_idx"]
         per = img0[0].numel()
 
         def reset_state():
-            img.copy_(img0)
-            if cfg:
-                x_buf[b:].copy_(img0)
+            r.seed()
             step_idx.zero_()                               # row 0 is of order 1: the ring's contents are dead from here
             t_buf.fill_(t_first)
 
@@ -224,16 +218,10 @@ class DPMSolverSampler(DDIMSampler):
                                    ring.data_ptr(), img.data_ptr(), pred_x0.data_ptr(), per, b, t_buf.data_ptr(), n_ts, 1, S,
                                    max_order, torch.cuda.current_stream().cuda_stream)
             L.check(rc, "ldmk_dpm_step")
-            if cfg:
-                x_buf[b:].copy_(img)                       # both guidance halves see the same latent (dpm_solver.py:340)
+            r.share_latent()                               # (dpm_solver.py:340)
 
         reset_state()
-        step = one_step
-        if use_graph:
-            if st["graph"] is None:
-                st["graph"] = GraphedProgram(one_step)
-                reset_state()                              # warm-up + capture advanced the device state
-            step = st["graph"].replay
+        step = r.stepper(st, one_step, reset_state, use_graph)
         x_inter = [img0.clone()] if want_inter else None
         for _ in range(S):
             step()

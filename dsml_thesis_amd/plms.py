@@ -2,8 +2,9 @@
   face_reenactment/ldm/models/diffusion/plms.py:11-236 (the talking-face tree carries an identical copy).
 
 Same call surface (`make_schedule`, `sample`, `plms_sampling`, `p_sample_plms`).  Everything before the first step -- conditioning
-split, guidance doubling, 'adm' labels, launch program or patch-wise evaluator, context program -- is `DDIMSampler._prepare_run`;
-the loop differs in two things.  The update is `ldmk_plms_step`: the DDIM update applied to an Adams-Bashforth combination of the
+split, guidance doubling, 'adm' labels, launch program or patch-wise evaluator, context program -- is `sampling_loop.prepare_run`
+(through `DDIMSampler._prepare_run`), and the option handling, loop state and graph capture are that module's too; the loop differs
+from DDIM's in two things.  The update is `ldmk_plms_step`: the DDIM update applied to an Adams-Bashforth combination of the
 current and up to three past model outputs, which stay in a device ring next to a device count of how many are stored.  And the
 first step evaluates the UNet twice (Euler predictor at t, corrector at t_next), so it runs as eager launches; steps 1 .. n-1 are one
 captured graph (UNet program + one multistep launch) whose order follows the device count.  Additions over the reference:
@@ -12,8 +13,8 @@ captured graph (UNet program + one multistep launch) whose order follows the dev
 import torch
 
 from . import lib as L
+from . import sampling_loop as SL
 from .ddim import DDIMSampler
-from .engine import GraphedProgram
 from .unet import rerun_if_flags_tripped
 
 
@@ -36,13 +37,9 @@ class PLMSSampler(DDIMSampler):
                noise_dropout=0., score_corrector=None, corrector_kwargs=None, verbose=True, x_T=None,
                log_every_t=100, unconditional_guidance_scale=1., unconditional_conditioning=None,
                use_graph=False, policy_batch=None, **kwargs):
-        if conditioning is None and getattr(self.model.model, "conditioning_key", "crossattn") is not None:
-            raise L.LdmkError("PLMSSampler.sample: conditioning is required (this model is cross-attention / concat conditioned).  "
+        SL.check_conditioning(self.model, conditioning, batch_size,
+                              "PLMSSampler.sample: conditioning is required (this model is cross-attention / concat conditioned).  "
                               "Only an unconditional LDM (cond_stage_config '__is_unconditional__') samples with conditioning=None")
-        ctx, cat0 = self._split_cond(conditioning)
-        first = ctx if ctx is not None else cat0
-        if first is not None and first.shape[0] != batch_size:
-            print(f"Warning: Got {first.shape[0]} conditionings but batch-size is {batch_size}")
         self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
         C_, H, W_ = shape
         size = (batch_size, C_, H, W_)
@@ -72,112 +69,70 @@ class PLMSSampler(DDIMSampler):
     def _plms_loop(self, cond, shape, x_T, callback, timesteps, quantize_denoised, mask, x0, img_callback, log_every_t, score_corrector,
                    corrector_kwargs, unconditional_guidance_scale, unconditional_conditioning, use_graph, policy_batch, mask_noise):
         r = self._prepare_run(cond, shape, x_T, unconditional_guidance_scale, unconditional_conditioning, policy_batch, "plms")
-        dev, b, img0, cfg, pg, x_buf, eps, run_net, loops = r.dev, r.b, r.img0, r.cfg, r.pg, r.x_buf, r.eps, r.run_net, r.loops
+        dev, b, img0, pg, img, run_net = r.dev, r.b, r.img0, r.pg, r.img, r.run_net
         S = self.ddim_timesteps.shape[0]
         lib = pg.lib
         t_buf = pg.inputs["t"]
         n_ts = t_buf.numel()
-        img = x_buf[:b]                                    # the latent lives in the UNet's input buffer, as in the DDIM loop
-        if mask is not None:
-            assert x0 is not None, "mask needs x0 (plms.py:148)"
-            mask = mask.to(dev, torch.float32).expand(shape).contiguous()
-            x0 = x0.to(dev, torch.float32)
         if score_corrector is not None:
-            assert self.model.parameterization == "eps"
             use_graph = False                              # a host callback sits inside the step
         extras = mask is not None or quantize_denoised or score_corrector is not None
         table, ts_table, tsteps = self._table, self._ts_table, self.ddim_timesteps
         n_run = S if timesteps is None else int(min(timesteps / S, 1) * S) - 1
         assert 0 < n_run <= S, (n_run, S)
         use_graph = bool(use_graph) and n_run > 1          # (one step: the eager first step is the whole run)
-        lkey = (cfg, float(unconditional_guidance_scale), self._sched_key, use_graph, n_run)
-        st = None if extras else loops.get(lkey)           # (option runs capture their own tensors: never cached)
-        if st is None:
-            # ring[k % 3] = the output of schedule index k; `count` = how many of them are stored (ldmk_plms_step)
-            st = dict(pred_x0=torch.empty_like(img0), keep=torch.empty_like(img0), ring=torch.empty((3,) + tuple(img0.shape), device=dev),
-                      step_idx=torch.zeros(1, dtype=torch.int32, device=dev), count=torch.zeros(1, dtype=torch.int32, device=dev),
-                      graph=None)
-            if not extras:
-                loops[lkey] = st
+        scale = float(unconditional_guidance_scale)
+        # ring[k % 3] = the output of schedule index k; `count` = how many of them are stored (ldmk_plms_step)
+        st = r.state((r.cfg, scale, self._sched_key, use_graph, n_run), lambda: dict(
+            pred_x0=torch.empty_like(img0), keep=torch.empty_like(img0), ring=torch.empty((3,) + tuple(img0.shape), device=dev),
+            step_idx=torch.zeros(1, dtype=torch.int32, device=dev), count=torch.zeros(1, dtype=torch.int32, device=dev)),
+            cached=not extras)
         pred_x0, keep, ring, step_idx, count = st["pred_x0"], st["keep"], st["ring"], st["step_idx"], st["count"]
         per = img0[0].numel()
-        scale = float(unconditional_guidance_scale)
+        blend = SL.MaskBlend(r, self.model, mask, x0, mask_noise) if mask is not None else None
+        score = SL.score_source(r, self.model, score_corrector, corrector_kwargs, cond, scale, t_buf)
 
         def reset_state():
-            img.copy_(img0)
-            if cfg:
-                x_buf[b:].copy_(img0)
+            r.seed()
             step_idx.fill_(n_run - 1)
             count.zero_()                                  # the ring's contents are dead without it
             t_buf.fill_(int(tsteps[n_run - 1]))
 
-        mnz = torch.zeros_like(img0) if mask is not None else None      # (zeros: the graph warm-up steps run before the first fill)
-        sqrt_ac, sqrt_1mac = self.model.sqrt_alphas_cumprod, self.model.sqrt_one_minus_alphas_cumprod
-        eps_c = torch.empty_like(img0) if score_corrector is not None else None
-
-        def blend():                                       # plms.py:147-150, timestep read from the device-side vector
-            tcur = t_buf[:b]
-            img_orig = (sqrt_ac.gather(-1, tcur).view(b, 1, 1, 1) * x0 + sqrt_1mac.gather(-1, tcur).view(b, 1, 1, 1) * mnz)
-            img.copy_(img_orig * mask + (1. - mask) * img)
-            if cfg:
-                x_buf[b:].copy_(img)
-
         def update(mode, x_in):
             """The model output in `eps` -> one ldmk_plms_step launch (+ advance) -> the quantisation fix-up."""
             a_prev = table[step_idx.long(), 1] if quantize_denoised else None      # read before the kernel advances the counter
-            e_ptr, k_cfg = eps.data_ptr(), (1 if cfg else 0)
-            if score_corrector is not None:                # plms.py:188-190 acts on the guidance-combined score
-                e_t = eps[:b] if not cfg else eps[:b] + scale * (eps[b:] - eps[:b])
-                eps_c.copy_(score_corrector.modify_score(self.model, e_t, img.clone(), t_buf[:b].clone(), cond, **(corrector_kwargs or {})))
-                e_ptr, k_cfg = eps_c.data_ptr(), 0
+            e_ptr, k_cfg = score()
             rc = lib.ldmk_plms_step(x_in.data_ptr(), e_ptr, table.data_ptr(), step_idx.data_ptr(), count.data_ptr(), scale, k_cfg,
                                     mode, ring.data_ptr(), keep.data_ptr() if mode == L.PLMS_PREDICTOR else 0, img.data_ptr(),
                                     pred_x0.data_ptr(), per, b, ts_table.data_ptr(), t_buf.data_ptr(), n_ts, 1, S,
                                     torch.cuda.current_stream().cuda_stream)
             L.check(rc, "ldmk_plms_step")
-            if quantize_denoised:                          # x_prev = sqrt(a_prev) Q(pred_x0) + dir_xt (plms.py:208-215)
-                q = self.model._quantize_denoised(pred_x0)
-                img.add_(torch.sqrt(a_prev) * (q - pred_x0))
-                pred_x0.copy_(q)
-            if cfg:
-                x_buf[b:].copy_(img)                       # both CFG halves see the same latent (plms.py:182)
+            if quantize_denoised:
+                SL.quantize_fixup(self.model, img, pred_x0, a_prev)
+            r.share_latent()
 
         def first_step():                                  # two UNet evaluations (plms.py:219-223): eager launches
-            if mask is not None:
-                blend()
+            if blend is not None:
+                blend.blend(t_buf)
             run_net()
             update(L.PLMS_PREDICTOR, img)                  # img <- the Euler prediction, keep <- img, t <- t_next
             run_net()
             update(L.PLMS_CORRECTOR, keep)
 
         def multistep():
-            if mask is not None:
-                blend()
+            if blend is not None:
+                blend.blend(t_buf)
             run_net()
             update(L.PLMS_MULTISTEP, img)
 
         reset_state()
-        step = multistep
-        if use_graph:
-            if st["graph"] is None:
-                if mask is not None and mask_noise is None:
-                    def step_with_noise():
-                        mnz.normal_()
-                        multistep()
-                    st["graph"] = GraphedProgram(step_with_noise)
-                else:
-                    st["graph"] = GraphedProgram(multistep)
-                reset_state()                              # warm-up + capture advanced the device state
-            step = st["graph"].replay
-
+        step = r.stepper(st, multistep, reset_state, use_graph, blend.draw if blend is not None else None)
         intermediates = {"x_inter": [img0], "pred_x0": [img0]}
         for i in range(n_run):
-            index = n_run - i - 1
-            if mask is not None:
-                if mask_noise is not None:
-                    mnz.copy_(mask_noise[i])
-                elif i == 0 or not use_graph:
-                    mnz.normal_()
+            if blend is not None:
+                blend.feed(i)
+                if i == 0 or not use_graph:                # (the first step is eager; a captured multistep draws inside)
+                    blend.draw()
             if i == 0:
                 first_step()
             else:
@@ -186,7 +141,7 @@ class PLMSSampler(DDIMSampler):
                 callback(i)
             if img_callback:
                 img_callback(pred_x0, i)
-            if index % log_every_t == 0 or index == n_run - 1:
+            if SL.log_step(n_run - i - 1, log_every_t, n_run):
                 intermediates["x_inter"].append(img.clone())
                 intermediates["pred_x0"].append(pred_x0.clone())
         return img.clone(), intermediates
@@ -218,9 +173,7 @@ class PLMSSampler(DDIMSampler):
                    scale, 1 if cfg else 0, mode, ring.data_ptr(), 0, x_prev.data_ptr(), pred_x0.data_ptr(), x[0].numel(), b, 0, 0, 0, 0, 0,
                    torch.cuda.current_stream().cuda_stream)
             if quantize_denoised:                                               # plms.py:208-209
-                q = self.model._quantize_denoised(pred_x0)
-                x_prev.add_(torch.sqrt(table[index, 1]) * (q - pred_x0))
-                pred_x0.copy_(q)
+                SL.quantize_fixup(self.model, x_prev, pred_x0, table[index, 1])
 
         if old_eps:
             update(L.PLMS_MULTISTEP, x, x, t)

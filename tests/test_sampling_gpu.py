@@ -727,6 +727,34 @@ def test_p_sample_loop_graph_and_full_length(fr):
     assert out.shape == (2, 3, 32, 32) and torch.isfinite(out).all()
 
 
+def test_p_sample_loop_keeps_the_policy_batch_a_sampler_left(fr):
+    """p_sample_loop has no `policy_batch=`: it prepares its run like the samplers do (sampling_loop.prepare_run) but with "keep",
+    so the tile plans are those of whatever `unet.policy_batch` the last DDIMSampler.sample left -- bit for bit the run made with
+    that value set by hand -- and it leaves the value alone.  With a noise list (eager) and with seeded draws inside the graph."""
+    from dsml_thesis_amd.ddim import DDIMSampler
+    c, _ = _cond(fr)
+    xT = rnd(51, 2, 3, 32, 32).cuda()
+    noise = list(T(golden("g5_sampling_fr.npz")["p_sample_loop_noise"]).cuda())
+    unet = fr.model.diffusion_model
+    before = unet.policy_batch
+
+    def runs():
+        torch.manual_seed(11)
+        return [fr.p_sample_loop(c, (2, 3, 32, 32), x_T=xT, timesteps=3, verbose=False, **kw) for kw in (dict(noise=noise), dict(use_graph=True))]
+    try:
+        unet.policy_batch = 4
+        by_hand = runs()
+        unet.policy_batch = None
+        DDIMSampler(fr).sample(S=4, batch_size=2, shape=[3, 32, 32], conditioning=c, eta=0.0, x_T=xT, verbose=False, policy_batch=4)
+        assert unet.policy_batch == 4
+        after = runs()
+        assert unet.policy_batch == 4
+        for a, b in zip(after, by_hand):
+            assert torch.isfinite(a).all() and torch.equal(a, b)
+    finally:
+        unet.policy_batch = before
+
+
 def test_class_conditional_model_through_the_samplers():
     """conditioning_key 'adm' under the samplers (ddpm.py:1417-1419: the conditioning IS the class-label vector y): a real-surface
     LatentDiffusion around the class-conditional UNet (use_scale_shift_norm, resblock_updown), DDIMSampler.sample plain and with
