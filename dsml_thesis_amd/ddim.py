@@ -25,6 +25,7 @@ from .unet import rerun_if_flags_tripped
 class DDIMSampler(object):
     def __init__(self, model, schedule="linear", **kwargs):
         super().__init__()
+        SL.require_eps_model(model, type(self).__name__)
         self.model = model
         self.ddpm_num_timesteps = model.num_timesteps
         self.schedule = schedule

@@ -119,7 +119,9 @@ class LatentDiffusion(_Base):
                  original_elbo_weight=0., v_posterior=0., l_simple_weight=1., parameterization="eps",
                  scheduler_config=None, use_positional_encodings=False, learn_logvar=False, logvar_init=0., **kw):
         super().__init__()
-        assert parameterization == "eps", "the shipped configs are eps-prediction"
+        assert parameterization in ["eps", "x0"], 'currently only supporting "eps" and "x0"'    # ddpm.py:76
+        if loss_type not in ("l1", "l2"):
+            raise NotImplementedError(f"unknown loss type '{loss_type}'")                         # ddpm.py:333 (get_loss)
         self.num_timesteps_cond = 1 if num_timesteps_cond is None else num_timesteps_cond
         assert self.num_timesteps_cond <= timesteps
         if self.num_timesteps_cond != 1:
@@ -138,12 +140,19 @@ class LatentDiffusion(_Base):
         if self.use_ema:
             self.model_ema = LitEma(self.model)
         self.v_posterior = v_posterior
+        self.loss_type, self.l_simple_weight, self.original_elbo_weight = loss_type, l_simple_weight, original_elbo_weight
         if monitor is not None:
             self.monitor = monitor
         self.scale_by_std = scale_by_std
         self.register_schedule(given_betas=given_betas, beta_schedule=beta_schedule, timesteps=timesteps,
                                linear_start=linear_start, linear_end=linear_end, cosine_s=cosine_s)
-        self.logvar = torch.full(fill_value=logvar_init, size=(self.num_timesteps,))
+        self.learn_logvar = learn_logvar
+        self.logvar = torch.full(fill_value=float(logvar_init), size=(self.num_timesteps,))
+        if learn_logvar:       # ddpm.py:111-114: a parameter (state dict, .to(device)) only when learned, else a plain tensor
+            self.logvar = nn.Parameter(self.logvar, requires_grad=True)
+        # the default objective (eps, l2, weight 1, no VLB term, fixed logvar 0) keeps its own launches (ldmk_mse_grad)
+        self._default_objective = (parameterization == "eps" and loss_type == "l2" and float(l_simple_weight) == 1.0 and
+                                   float(original_elbo_weight) == 0.0 and not learn_logvar and float(logvar_init) == 0.0)
         self.concat_mode, self.cond_stage_trainable, self.cond_stage_key = concat_mode, cond_stage_trainable, cond_stage_key
         if not scale_by_std:
             self.scale_factor = scale_factor
@@ -152,9 +161,6 @@ class LatentDiffusion(_Base):
         self.instantiate_first_stage(first_stage_config)
         self.instantiate_cond_stage(cond_stage_config)
         self.cond_stage_forward = cond_stage_forward
-        self.learn_logvar = learn_logvar
-        if learn_logvar:
-            raise NotImplementedError("learn_logvar=True is unused by the shipped configs")
         self.use_scheduler = scheduler_config is not None
         self.scheduler_config = scheduler_config
         self.restarted_from_ckpt = False
@@ -169,8 +175,8 @@ class LatentDiffusion(_Base):
             beta_schedule, timesteps, linear_start=linear_start, linear_end=linear_end, cosine_s=cosine_s)
         self.num_timesteps = int(np.asarray(betas).shape[0])
         self.linear_start, self.linear_end = linear_start, linear_end
-        for k, v in S_.schedule_buffers(betas, self.v_posterior).items():
-            self.register_buffer(k, v)
+        for k, v in S_.schedule_buffers(betas, self.v_posterior, self.parameterization).items():
+            self.register_buffer(k, v, persistent=k != "lvlb_weights")      # ddpm.py:168: lvlb_weights stays out of the state dict
         self.shorten_cond_schedule = False
         self._ddpm_tables = None
 
@@ -423,8 +429,12 @@ class LatentDiffusion(_Base):
     # ---- ancestral sampler -----------------------------------------------------------------------------
     def _ddpm_device_tables(self):
         if self._ddpm_tables is None or self._ddpm_tables[0].device != self.betas.device:
-            tab = torch.stack([self.sqrt_recip_alphas_cumprod, self.sqrt_recipm1_alphas_cumprod,
-                               self.posterior_mean_coef1, self.posterior_mean_coef2], 1).contiguous()
+            # ldmk_ddpm_step forms x_recon = A x - B out from columns 0, 1.  x0-prediction (ddpm.py:1064-1065: x_recon = out):
+            # A = 0, B = -1, exact for finite x
+            A, B = self.sqrt_recip_alphas_cumprod, self.sqrt_recipm1_alphas_cumprod
+            if self.parameterization == "x0":
+                A, B = torch.zeros_like(A), torch.full_like(B, -1.0)
+            tab = torch.stack([A, B, self.posterior_mean_coef1, self.posterior_mean_coef2], 1).contiguous()
             self._ddpm_tables = (tab, self.posterior_log_variance_clipped.contiguous())
         return self._ddpm_tables
 
@@ -500,7 +510,10 @@ class LatentDiffusion(_Base):
             assert self.parameterization == "eps"
             eps = score_corrector.modify_score(self, eps, x, t, c, **(corrector_kwargs or {}))
         ex = lambda a: a.gather(-1, t).view(-1, 1, 1, 1)                    # extract_into_tensor, util.py:96-99
-        x_recon = ex(self.sqrt_recip_alphas_cumprod) * x - ex(self.sqrt_recipm1_alphas_cumprod) * eps      # :215-219
+        if self.parameterization == "x0":                                   # ddpm.py:1064-1065: the output IS the estimate
+            x_recon = eps
+        else:
+            x_recon = ex(self.sqrt_recip_alphas_cumprod) * x - ex(self.sqrt_recipm1_alphas_cumprod) * eps  # :215-219
         if clip_denoised:
             x_recon = x_recon.clamp(-1., 1.)
         if quantize_denoised:
@@ -653,6 +666,9 @@ class LatentDiffusion(_Base):
         for key in ("_cond_opt", "_audio_opt"):
             opt = getattr(self, key, None)
             st[key] = None if opt is None else opt.state_dict()
+        if self.learn_logvar:
+            m, v = getattr(self, "_logvar_m", None), getattr(self, "_logvar_v", None)
+            st["logvar"] = dict(value=self.logvar.data.clone(), m=None if m is None else m.clone(), v=None if v is None else v.clone())
         return st
 
     def load_training_state(self, st, lr=1e-4, weight_decay=1e-2):
@@ -660,6 +676,10 @@ class LatentDiffusion(_Base):
         tr.load_optimizer_state(st["unet"])
         if st.get("ema_flat") is not None and self.use_ema:
             self._ema_flat.copy_(st["ema_flat"])
+        if st.get("logvar") is not None and self.learn_logvar:
+            lv = self.logvar.data
+            lv.copy_(st["logvar"]["value"])
+            self._logvar_m, self._logvar_v = (None if st["logvar"][k] is None else st["logvar"][k].to(lv.device).clone() for k in "mv")
         owners = {"_cond_opt": getattr(self, "cond_stage_model_1", None) or self.cond_stage_model,
                   "_audio_opt": getattr(self, "cond_stage_model_2", None)}
         for key, owner in owners.items():
@@ -675,12 +695,27 @@ class LatentDiffusion(_Base):
             cond = torch.cat(list(cond), 1)
         return cond
 
-    def p_losses(self, x_start, cond, t, noise=None, c_concat=None, reduce_world=1):
-        """ddpm.py:1014-1047 for the shipped settings (eps-prediction, l2, l_simple_weight 1, fixed logvar 0,
-        original_elbo_weight 0): loss = mean((eps_theta(q_sample(x0, t, noise), t, cond) - noise)^2).
+    def _logvar_device(self, dev):
+        """`logvar` where the kernels read it: the parameter itself when learned (it follows .to(device)); else a device copy of
+        the plain tensor, which stays where the constructor left it, as in the reference (ddpm.py:1032 moves logvar[t])."""
+        if self.learn_logvar:
+            return self.logvar.data
+        cached = getattr(self, "_logvar_dev", None)
+        if cached is None or cached.device != dev:
+            cached = self._logvar_dev = self.logvar.detach().to(dev, torch.float32).contiguous()
+        return cached
+
+    def p_losses(self, x_start, cond, t, noise=None, c_concat=None, reduce_world=1, forward_only=False, prefix=None):
+        """ddpm.py:1014-1047.  The default configuration (eps-prediction, l2, l_simple_weight 1, fixed logvar 0,
+        original_elbo_weight 0): loss = mean((eps_theta(q_sample(x0, t, noise), t, cond) - noise)^2) on ldmk_mse_grad, and the
+        dictionary holds `loss_simple` and `loss` (the logged-only `loss_vlb` entry is not computed).  Any other setting --
+        x0-prediction (the target is x_start), l1, a weight, a VLB term, a fixed non-zero or a learned logvar -- runs the one
+        objective kernel (ldmk_diffusion_loss) and returns the reference's full dictionary: `loss_simple`, `loss_gamma` and
+        `logvar` when learned, `loss_vlb`, `loss`; the gradient w.r.t. a learned logvar is left in `self._dlogvar` (T,).
+        `forward_only` (validation): always the objective kernel, no gradient, nothing of the training state is written.
         Runs forward AND backward on the HIP kernels; gradients are left in `self.trainer().P.grad` (UNet, packed
         layout) and `self.trainer().dctx` (w.r.t. the context tokens; None without a context).  Returns (loss, loss_dict) like
-        the reference; the logged-only `loss_vlb` entry is not computed.
+        the reference.
         `cond` by conditioning_key (DiffusionWrapper, ddpm.py:1404-1423): None -> nothing; 'concat' -> the tensor(s) to concatenate
         on the channel axis; 'adm' -> class labels (B,) in any form apply_model accepts (y, [y], {"c_crossattn": [y]});
         'crossattn' / 'hybrid' -> the context tokens."""
@@ -701,10 +736,86 @@ class LatentDiffusion(_Base):
             raise NotImplementedError(f"p_losses: conditioning_key {key!r}")
         if isinstance(c_concat, (list, tuple)):
             c_concat = torch.cat(list(c_concat), 1)
+        prefix = prefix or ("train" if self.training else "val")
+        objective = None
+        if forward_only or not self._default_objective:
+            dev = x_start.device
+            objective = dict(parameterization=self.parameterization, loss_type=self.loss_type, l_simple_weight=self.l_simple_weight,
+                             original_elbo_weight=self.original_elbo_weight, logvar=self._logvar_device(dev),
+                             lvlb_weights=self.lvlb_weights, learn_logvar=self.learn_logvar, forward_only=forward_only)
         loss = tr.p_losses(x_start.float(), ctx, t, noise.float(), self.sqrt_alphas_cumprod, self.sqrt_one_minus_alphas_cumprod,
-                           c_concat=c_concat, reduce_world=reduce_world, y=y)
-        prefix = "train" if self.training else "val"
-        return loss, {f"{prefix}_loss_simple": loss, f"{prefix}_loss": loss}
+                           c_concat=c_concat, reduce_world=reduce_world, y=y, objective=objective)
+        if objective is None:
+            return loss, {f"{prefix}_loss_simple": loss, f"{prefix}_loss": loss}
+        out = tr.objective_out
+        sc = out["scalars"]
+        loss_dict = {f"{prefix}_loss_simple": sc[1:2]}
+        if self.learn_logvar:                                               # ddpm.py:1035-1037
+            loss_dict[f"{prefix}_loss_gamma"] = sc[2:3]
+            loss_dict["logvar"] = self.logvar.data.mean()
+        loss_dict[f"{prefix}_loss_vlb"] = sc[3:4]
+        loss_dict[f"{prefix}_loss"] = loss
+        if not forward_only:
+            self._dlogvar = out["dlogvar"]
+        return loss, loss_dict
+
+    def _logvar_step(self, lr, weight_decay, world_size=1):
+        """The learned logvar sits in the same AdamW as the UNet in the reference (ddpm.py:1369-1372): ldmk_adamw over its T entries
+        with the UNet's lr, weight decay and step count, after averaging its gradient over the ranks the way dctx is.  Every
+        entry decays every step, whether a sample sat on it or not."""
+        if not self.learn_logvar or getattr(self, "_dlogvar", None) is None:
+            return
+        from . import train_ops as T
+        dlv = self._dlogvar
+        if world_size > 1:
+            import torch.distributed as dist
+            dist.all_reduce(dlv)
+            dlv = dlv / world_size
+        lv = self.logvar.data
+        if getattr(self, "_logvar_m", None) is None or self._logvar_m.device != lv.device:
+            self._logvar_m, self._logvar_v = torch.zeros_like(lv), torch.zeros_like(lv)
+        T.adamw_(lv, dlv.contiguous(), self._logvar_m, self._logvar_v, lr, (0.9, 0.999), 1e-8, weight_decay, self.trainer().P.step)
+
+    @torch.no_grad()
+    def _validate(self, run):
+        """ddpm.py:356-363: `run()` -> loss dict of one forward-only pass; once on the live weights, once on the EMA shadow
+        (keys + '_ema').  The shadow is copied into the trainer's flat parameter buffer for its pass and the live weights are
+        copied back after it: parameters, gradients, moments, step count and shadow end up bit for bit what they were."""
+        tr = self.trainer()
+        out = ema = dict(run())
+        if self.use_ema:                 # (without a shadow the reference's ema_scope is empty: its second pass repeats the first)
+            live = tr.P.flat.clone()
+            tr.P.flat.copy_(self._ema_flat)
+            try:
+                ema = run()
+            finally:
+                tr.P.flat.copy_(live)
+        return dict(out, **{k + "_ema": v for k, v in ema.items()})
+
+    @torch.no_grad()
+    def validation_step_latents(self, z, cond_batch, t=None, noise=None):
+        """The validation pass on already-encoded latents: forward only, through ldmk_diffusion_loss with no dpred, whatever the
+        objective.  -> {val_loss_simple, [val_loss_gamma, logvar,] val_loss_vlb, val_loss} + the same with '_ema' (use_ema)."""
+        t = torch.randint(0, self.num_timesteps, (z.shape[0],), device=z.device).long() if t is None else t
+        noise = torch.randn_like(z) if noise is None else noise
+        c = cond_batch
+        if self.cond_stage_trainable:
+            try:
+                c = self.cond_stage_model(cond_batch, training=False)
+            except TypeError:
+                c = self.get_learned_conditioning(cond_batch)
+        if self.model.conditioning_key in ("crossattn", "hybrid"):
+            c = self._context_tensor(c).detach()
+        return self._validate(lambda: self.p_losses(z, c, t, noise, forward_only=True, prefix="val")[1])
+
+    @torch.no_grad()
+    def validation_step(self, batch, batch_idx=0):
+        """ddpm.py:356-363: what `monitor: val/loss_simple_ema` reads."""
+        z, c = self.get_input(batch, self.first_stage_key)
+        d = self.validation_step_latents(z, c)
+        self.log_dict({k: v for k, v in d.items() if not k.endswith("_ema")}, prog_bar=False, logger=True, on_step=False, on_epoch=True)
+        self.log_dict({k: v for k, v in d.items() if k.endswith("_ema")}, prog_bar=False, logger=True, on_step=False, on_epoch=True)
+        return d
 
     def forward(self, x, c, *args, **kwargs):
         """ddpm.py:866-877: draw t, embed the condition when the conditioner is trainable, p_losses."""
@@ -734,6 +845,7 @@ class LatentDiffusion(_Base):
             ctx, cond_in = None, c
         loss, loss_dict = self.p_losses(z, cond_in, t, noise, reduce_world=world_size)   # bucketed all-reduce inside
         tr.adamw_step(lr, weight_decay=weight_decay)
+        self._logvar_step(lr, weight_decay, world_size)
         if self.cond_stage_trainable and ctx is not None and ctx.requires_grad and getattr(tr, "dctx", None) is not None:
             if self._cond_opt is None:
                 self._cond_opt = torch.optim.AdamW(self.cond_stage_model.parameters(), lr=lr, weight_decay=weight_decay)
@@ -791,6 +903,8 @@ class LatentDiffusion(_Base):
         if self.use_scheduler:
             assert "target" in self.scheduler_config
             self.lr_schedule = instantiate_from_config(self.scheduler_config).schedule
+        if self.learn_logvar:            # ddpm.py:1369-1371; stepped by ldmk_adamw next to the UNet (_logvar_step)
+            print("Diffusion model optimizing logvar")
         owner = self.cond_stage_model if self.cond_stage_model is not None else getattr(self, "cond_stage_model_1", None)
         if not self.cond_stage_trainable or owner is None:
             return None
@@ -896,9 +1010,24 @@ class LatentDiffusion2Cond(LatentDiffusion):
         from .ddim import C12, C34
         return {C12: torch.cat([c1, c2], 2), C34: torch.cat([z_mask, z_id], 1)}
 
-    def p_losses(self, x_start, cond12, cond34=None, t=None, noise=None):
+    def p_losses(self, x_start, cond12, cond34=None, t=None, noise=None, forward_only=False, prefix=None):
         """ddpm2cond.py p_losses(x_start, cond12, cond34, t): cross-attention tokens + channel-concat latents."""
-        return super().p_losses(x_start, cond12, t, noise=noise, c_concat=cond34)
+        return super().p_losses(x_start, cond12, t, noise=noise, c_concat=cond34, forward_only=forward_only, prefix=prefix)
+
+    @torch.no_grad()
+    def validation_step_latents(self, z, cond_batch, audio_feat, c34, t=None, noise=None, audio_window=None):
+        """The validation pass of the talking-face model, with training_step_latents' conditioning arguments: forward only, on the
+        live weights and on the EMA shadow (LatentDiffusion.validation_step_latents)."""
+        if audio_window is not None:
+            audio_feat = self.cond_stage_model_2(audio_window)
+        t = torch.randint(0, self.num_timesteps, (z.shape[0],), device=z.device).long() if t is None else t
+        noise = torch.randn_like(z) if noise is None else noise
+        try:
+            c1 = self.cond_stage_model_1(cond_batch, training=False)
+        except TypeError:
+            c1 = self.cond_stage_model_1(cond_batch)
+        c12 = torch.cat([c1.detach(), audio_feat.detach().float()], 2)
+        return self._validate(lambda: self.p_losses(z, c12, c34, t, noise, forward_only=True, prefix="val")[1])
 
     def training_step_latents(self, z, cond_batch, audio_feat, c34, lr, t=None, noise=None, world_size=1, weight_decay=1e-2,
                               audio_window=None):
@@ -922,6 +1051,7 @@ class LatentDiffusion2Cond(LatentDiffusion):
         if world_size > 1:
             tr.all_reduce_grads(world_size)
         tr.adamw_step(lr, weight_decay=weight_decay)
+        self._logvar_step(lr, weight_decay, world_size)
         dc12 = tr.dctx.view_as(c12)
         if self.cond_stage_trainable and c1.requires_grad:
             if getattr(self, "_cond_opt", None) is None:

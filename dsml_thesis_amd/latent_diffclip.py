@@ -26,6 +26,8 @@ class LatentDiffusionCLIP(LatentDiffusion):
         if eta != 0.0 or quantize_x0 or score_corrector is not None:
             raise NotImplementedError("LatentDiffusionCLIP: eta = 0, no x0 quantisation, no score corrector (shipped settings)")
         super().__init__(first_stage_config, cond_stage_config, **kwargs)
+        from .sampling_loop import require_eps_model
+        require_eps_model(self, type(self).__name__)
         from .autoencoder import VQModelInterface
         if not isinstance(self.first_stage_model, VQModelInterface):
             raise NotImplementedError(f"{type(self).__name__}: the fine-tune decodes differentiably through a VQ first stage; "

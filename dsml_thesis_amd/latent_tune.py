@@ -32,6 +32,8 @@ class LatentDiffusionTune(LatentDiffusion2Cond):
         assert concat_mode is False
         super().__init__(first_stage_config, cond_stage_config_1, cond_stage_config_2, cond_stage_trainable=cond_stage_trainable,
                          concat_mode=concat_mode, conditioning_key=conditioning_key, **kwargs)
+        from .sampling_loop import require_eps_model
+        require_eps_model(self, type(self).__name__)
         from .autoencoder import VQModelInterface
         if not isinstance(self.first_stage_model, VQModelInterface):
             raise NotImplementedError(f"{type(self).__name__}: the fine-tune decodes differentiably through a VQ first stage; "

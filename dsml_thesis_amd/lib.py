@@ -223,6 +223,10 @@ _SIGS = {
     "ldmk_gauss_kl_fwd": (C.c_int, [_fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp]),
     "ldmk_gauss_kl_bwd": (C.c_int, [_fp, _fp, _fp, C.c_float, _fp, C.c_int, C.c_int, C.c_int, _fp]),
     "ldmk_l1_sum_grad": (C.c_int, [_fp, _fp, _fp, C.c_longlong, C.c_float, _fp, _fp, _fp]),
+    # ---- the diffusion objective (l1 / l2, learned logvar, VLB)
+    "ldmk_diffusion_loss_scratch_elems": (C.c_longlong, [C.c_int]),
+    "ldmk_diffusion_loss": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                      C.c_float, C.c_float, _fp, _fp]),
 }
 # every symbol include/ldmk.h declares (checked by tests/test_abi.py against the header text)
 EXPORTED = [k for k in _SIGS if k not in ("ldmk_igemm_force_config", "ldmk_attn_force_qt")]

@@ -24,6 +24,16 @@ def is_adm(model):
     return getattr(model.model, "conditioning_key", None) == "adm"
 
 
+def require_eps_model(model, who):
+    """The DDIM, PLMS and DPM-Solver updates and the two fine-tunes take the network output as the noise estimate, as the reference's
+    do whatever the model's parameterization (ddim.py:165-191 reads e_t = apply_model(...)).  Over an x0-prediction model that
+    is a wrong sample, not an error, in the reference; here it is an error.  The ancestral loop (p_sample_loop) handles x0."""
+    p = getattr(model, "parameterization", "eps")
+    if p != "eps":
+        raise NotImplementedError(f"{who}: the model predicts {p!r}, and this update reads the network output as eps "
+                                  "(sample an x0-prediction model with LatentDiffusion.p_sample_loop / sample)")
+
+
 def labels(cond):
     """conditioning_key 'adm': the class-label vector y (B,) out of whatever form apply_model accepts (ddpm.py:893-994 wraps a
     tensor as c_crossattn = [y]; DiffusionWrapper takes c_crossattn[0], :1417-1419)."""

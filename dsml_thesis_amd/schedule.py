@@ -26,15 +26,31 @@ def make_beta_schedule(schedule, n_timestep, linear_start=1e-4, linear_end=2e-2,
     raise ValueError(f"schedule '{schedule}' unknown.")
 
 
-def schedule_buffers(betas, v_posterior=0.0):
-    """float64 math, float32 buffers, names as registered by DDPM.register_schedule."""
+def lvlb_weights(buffers, alphas, parameterization="eps"):
+    """The VLB weights of ddpm.py:159-168 from the float32 schedule buffers, in the reference's float32 torch arithmetic (and
+    with its x0 formula exactly as written there), entry 0 patched with entry 1.  Non-persistent in the reference."""
+    if parameterization == "eps":
+        w = buffers["betas"] ** 2 / (2 * buffers["posterior_variance"] * torch.tensor(alphas, dtype=torch.float32) *
+                                     (1 - buffers["alphas_cumprod"]))
+    elif parameterization == "x0":
+        ac = torch.Tensor(np.asarray(alphas).cumprod(axis=0))
+        w = 0.5 * torch.sqrt(ac) / (2. * 1 - ac)
+    else:
+        raise NotImplementedError("mu not supported")
+    w[0] = w[1]
+    return w
+
+
+def schedule_buffers(betas, v_posterior=0.0, parameterization=None):
+    """float64 math, float32 buffers, names as registered by DDPM.register_schedule.  `parameterization` ("eps" / "x0"): also
+    `lvlb_weights` (a non-persistent buffer of the reference: the caller keeps it out of the state dict)."""
     betas = np.asarray(betas, dtype=np.float64)
     alphas = 1.0 - betas
     ac = np.cumprod(alphas, axis=0)
     ac_prev = np.append(1.0, ac[:-1])
     f32 = lambda a: torch.tensor(a, dtype=torch.float32)
     pv = (1 - v_posterior) * betas * (1.0 - ac_prev) / (1.0 - ac) + v_posterior * betas
-    return dict(
+    out = dict(
         betas=f32(betas), alphas_cumprod=f32(ac), alphas_cumprod_prev=f32(ac_prev),
         sqrt_alphas_cumprod=f32(np.sqrt(ac)), sqrt_one_minus_alphas_cumprod=f32(np.sqrt(1.0 - ac)),
         log_one_minus_alphas_cumprod=f32(np.log(1.0 - ac)), sqrt_recip_alphas_cumprod=f32(np.sqrt(1.0 / ac)),
@@ -42,6 +58,9 @@ def schedule_buffers(betas, v_posterior=0.0):
         posterior_log_variance_clipped=f32(np.log(np.maximum(pv, 1e-20))),
         posterior_mean_coef1=f32(betas * np.sqrt(ac_prev) / (1.0 - ac)),
         posterior_mean_coef2=f32((1.0 - ac_prev) * np.sqrt(alphas) / (1.0 - ac)))
+    if parameterization is not None:
+        out["lvlb_weights"] = lvlb_weights(out, alphas, parameterization)
+    return out
 
 
 def make_ddim_timesteps(ddim_discr_method, num_ddim_timesteps, num_ddpm_timesteps):

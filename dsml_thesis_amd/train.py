@@ -742,9 +742,10 @@ class UNetTrainer:
         return out
 
     # ---- p_losses / optimizer -------------------------------------------------------------------------------
-    def p_losses(self, x_start, context, t, noise, sqrt_ac, sqrt_1mac, c_concat=None, reduce_world=1, y=None):
-        """ddpm.py:1014-1047 with parameterization 'eps', loss_type 'l2', l_simple_weight 1, no learned logvar,
-        original_elbo_weight 0: loss = mean((eps_theta(q_sample(x0,t,noise), t, c) - noise)^2); `c_concat` (masked-frame +
+    def p_losses(self, x_start, context, t, noise, sqrt_ac, sqrt_1mac, c_concat=None, reduce_world=1, y=None, objective=None):
+        """ddpm.py:1014-1047.  `objective` None: parameterization 'eps', loss_type 'l2', l_simple_weight 1, no learned logvar,
+        original_elbo_weight 0: loss = mean((eps_theta(q_sample(x0,t,noise), t, c) - noise)^2) on ldmk_mse_grad; any other
+        setting: the dict `_objective` describes, on ldmk_diffusion_loss.  `c_concat` (masked-frame +
         identity latents of the talking-face model) is concatenated to the noisy latent on the channel axis; `context` is None for
         a UNet without spatial transformers, `y` the class labels of a `num_classes` one.  Returns the loss
         (device scalar) after running forward + backward; gradients are in self.P.grad."""
@@ -752,12 +753,31 @@ class UNetTrainer:
         if c_concat is not None:         # TF DiffusionWrapper: torch.cat([x] + c_concat, dim=1), ddpm2cond.py:1309
             x_noisy = torch.cat([x_noisy, c_concat.float()], 1)
         self.forward(x_noisy, t, context, y=y)
+        if objective is not None:
+            return self._objective(objective, x_start, noise, t, reduce_world)
         n, co, H, W_ = noise.shape
         tgt = torch.zeros_like(self.eps_pad)
         tgt[..., :co] = noise.permute(0, 2, 3, 1)
         loss, deps = T.mse_grad(self.eps_pad, tgt, denom=noise.numel())
         self.backward(deps, reduce_world=reduce_world)
         return loss
+
+    def _objective(self, obj, x_start, noise, t, reduce_world):
+        """The full objective over the pass just run (ldmk_diffusion_loss): the target -- x_start under x0-prediction -- is read
+        in NCHW where it lies, dpred comes back in eps_pad's layout.  `obj`: parameterization, loss_type, l_simple_weight,
+        original_elbo_weight, logvar, lvlb_weights (device, (T,)), learn_logvar, forward_only.  The kernel's outputs stay in
+        `self.objective_out` (scalars = [loss, loss_simple, loss_gamma, loss_vlb], ls, dlogvar); returns the loss."""
+        target = (x_start if obj["parameterization"] == "x0" else noise).contiguous()
+        fwd_only = bool(obj.get("forward_only"))
+        out = T.diffusion_loss(self.eps_pad, target, t.to(torch.int64).contiguous(), obj["logvar"], obj["lvlb_weights"],
+                               obj["loss_type"], obj["l_simple_weight"], obj["original_elbo_weight"], want_dpred=not fwd_only,
+                               want_dlogvar=bool(obj.get("learn_logvar")) and not fwd_only)
+        self.objective_out = out
+        if fwd_only:                                   # nothing walks the tape: let the saved activations go
+            self.tape, self.G, self.ginit, self.last_pass = [], {}, set(), None
+        else:
+            self.backward(out["dpred"], reduce_world=reduce_world)
+        return out["scalars"][0:1]
 
     def adamw_step(self, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
         P = self.P

@@ -311,6 +311,44 @@ def l1_grad(pred, target, dpred=None, loss=None, denom=0):
     return loss, dpred
 
 
+LOSS_TYPES = {"l1": 1, "l2": 2}
+
+
+def diffusion_loss(pred_pad, target, t, logvar, lvlb_weights, loss_type="l2", l_simple_weight=1.0, original_elbo_weight=0.0,
+                   want_dpred=True, want_dlogvar=True, dpred=None):
+    """The full objective of p_losses (ddpm.py:1014-1047) in one launch pair (ldmk_diffusion_loss): pred_pad (n,H,W,32) or
+    (n,H*W,32) channel-padded NHWC, target (n,c,H,W) NCHW read in place, t (n,) int64, logvar / lvlb_weights (T,).
+    -> dict(scalars=[loss, loss_simple, loss_gamma, loss_vlb] (4,), ls (n,), dpred like pred_pad or None, dlogvar (T,) or None)."""
+    for name, x in (("pred", pred_pad), ("target", target), ("logvar", logvar), ("lvlb_weights", lvlb_weights), ("dpred", dpred)):
+        ops._chk(x, f"diffusion_loss {name}")
+    if not (t.is_cuda and t.is_contiguous()):
+        raise L.LdmkError("diffusion_loss t: expected a contiguous CUDA tensor")
+    if loss_type not in LOSS_TYPES:
+        raise NotImplementedError(f"unknown loss type '{loss_type}'")
+    n, c = target.shape[0], target.shape[1]
+    hw = target[0, 0].numel()
+    T_ = logvar.numel()
+    if pred_pad.shape[-1] != 32 or pred_pad.numel() != n * hw * 32 or t.dtype != torch.int64 or t.numel() != n \
+            or lvlb_weights.numel() != T_ or logvar.dtype != torch.float32 or lvlb_weights.dtype != torch.float32 \
+            or pred_pad.dtype != torch.float32 or target.dtype != torch.float32:
+        raise ValueError(f"diffusion_loss: pred {tuple(pred_pad.shape)} {pred_pad.dtype}, target {tuple(target.shape)} {target.dtype}, "
+                         f"t {tuple(t.shape)} {t.dtype}, logvar {tuple(logvar.shape)}, lvlb_weights {tuple(lvlb_weights.shape)}")
+    dev = pred_pad.device
+    if want_dpred and dpred is None:
+        dpred = torch.empty_like(pred_pad)
+    elif not want_dpred:
+        dpred = None
+    if dpred is not None and (dpred.shape != pred_pad.shape or dpred.dtype != torch.float32):
+        raise ValueError(f"diffusion_loss: dpred {tuple(dpred.shape)} against pred {tuple(pred_pad.shape)}")
+    dlogvar = _f32(T_, device=dev) if want_dlogvar else None
+    scalars, ls = _f32(4, device=dev), _f32(n, device=dev)
+    scratch = torch.empty(L.load().ldmk_diffusion_loss_scratch_elems(n), device=dev, dtype=torch.float64)
+    L.call("ldmk_diffusion_loss", _ptr(pred_pad), _ptr(target), _ptr(t), _ptr(logvar), _ptr(lvlb_weights), _ptr(dpred), _ptr(dlogvar),
+           _ptr(scalars), _ptr(ls), n, c, hw, T_, LOSS_TYPES[loss_type], float(l_simple_weight), float(original_elbo_weight),
+           _ptr(scratch), stream())
+    return dict(scalars=scalars, ls=ls, dpred=dpred, dlogvar=dlogvar)
+
+
 def _vq_dims(z, codebook, idx):
     ops._chk(z, "vq z")
     ops._chk(codebook, "vq codebook")

@@ -855,6 +855,29 @@ int ldmk_gauss_kl_bwd(const float* moments, const float* noise, const float* dz,
 int ldmk_l1_sum_grad(const float* pred, const float* target, float* dpred, long long n, float g, float* sum, double* scratch,
                      void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The diffusion objective of LatentDiffusion.p_losses (ddpm.py:1014-1047) beyond the default one (csrc/objective.hip); the
+ * conventions of the first-stage kernels above (no float atomics, double partials in one fixed order, bitwise reproducible).
+ * pred (n, hw, 32): the UNet output in the trainer's channel-padded NHWC rows, c <= 32 real channels; target (n, c, hw) NCHW,
+ * read where it lies (noise under eps-prediction, x_start under x0); t int64 [n] (clamped into [0, T)); logvar, lvlb_weights [T].
+ * With d = pred - target, per = c hw, ls_b = mean_i f(d_bi) (loss_type 1: f = |d|; 2: f = d^2), lv_b = logvar[t_b],
+ * w_b = lvlb_weights[t_b]:
+ *   scalars[0] loss        = l_simple_weight loss_gamma + original_elbo_weight loss_vlb
+ *   scalars[1] loss_simple = mean_b ls_b
+ *   scalars[2] loss_gamma  = mean_b (ls_b e^{-lv_b} + lv_b)
+ *   scalars[3] loss_vlb    = mean_b (w_b ls_b)
+ *   ls[b]      = ls_b
+ *   dpred (n, hw, 32) = (l_simple_weight e^{-lv_b} + original_elbo_weight w_b) / (n per) f'(d), f' = sign(d) (sign(0) = 0) or 2d;
+ *              the 32 - c pad lanes are written as exact zeros.  NULL: forward only, the scalars keep their bits.
+ *   dlogvar[tau] = sum_{b: t_b = tau} (l_simple_weight / n) (1 - ls_b e^{-lv_b}), dense over [0, T), zero where no sample
+ *              sits, summed in sample order.  NULL: skipped.
+ * The per-sample weights are formed in double from the double ls_b and rounded once.  pred and dpred are 16-byte aligned.
+ * scratch = ldmk_diffusion_loss_scratch_elems(n) doubles. */
+long long ldmk_diffusion_loss_scratch_elems(int n);
+int ldmk_diffusion_loss(const float* pred, const float* target, const long long* t, const float* logvar,
+                        const float* lvlb_weights, float* dpred, float* dlogvar, float* scalars, float* ls, int n, int c, int hw,
+                        int T, int loss_type, float l_simple_weight, float original_elbo_weight, double* scratch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

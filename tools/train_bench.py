@@ -1,6 +1,11 @@
 """BASELINE config 5 rehearsal on one GPU: UNet training step (p_losses forward + backward + AdamW + EMA), fp32.
 
   python tools/train_bench.py [--batch 16] --latent 32 [--graph] [--steps 10] [--bf16] [--unet shipped|uncond|adm|heads64]
+                              [--objective default|full]
+--objective full: the step with the whole objective of p_losses (l1, l_simple_weight 0.8, original_elbo_weight 10, a learned
+logvar with its AdamW step) on ldmk_diffusion_loss instead of the default one on ldmk_mse_grad.  Either way the result also
+carries the loss stage alone, timed with device events over the pass's own output in both forms, alternating:
+`loss_stage_us_default` (zeroed padded target + permute + ldmk_mse_grad) and `loss_stage_us_full` (ldmk_diffusion_loss).
 --unet: the shipped spatial-transformer UNet (default), `uncond` (BASELINE configs[0]: synth.UNCOND_UNET, AttentionBlocks, no
 context; 64x64x4 latent), `adm` (synth.ADM_TRAIN_UNET: scale-shift norm + class labels at the shipped widths) or `heads64` (the
 shipped 64x64x4 UNet, synth.NS_UNET, with num_head_channels = 64: the flash kernels of csrc/attention_train.hip; implies
@@ -137,6 +142,7 @@ def main():
     ap.add_argument("--graph", action="store_true")
     ap.add_argument("--bf16", action="store_true", help="bf16 GEMM operands (UNetTrainer compute='bf16')")
     ap.add_argument("--unet", default="shipped", choices=["shipped", "uncond", "adm", "heads64"])
+    ap.add_argument("--objective", default="default", choices=["default", "full"])
     a = ap.parse_args()
     if a.tune:
         return tune_bench(a)
@@ -166,6 +172,13 @@ def main():
                                                                      linear_start=synth.SCHEDULE["linear_start"],
                                                                      linear_end=synth.SCHEDULE["linear_end"]), 0.0)
         sa, sb = bufs["sqrt_alphas_cumprod"].to(dev), bufs["sqrt_one_minus_alphas_cumprod"].to(dev)
+    from dsml_thesis_amd import schedule as S_, synth as Y_, train_ops as T
+    lvlb = S_.schedule_buffers(S_.make_beta_schedule("linear", Y_.SCHEDULE["timesteps"], linear_start=Y_.SCHEDULE["linear_start"],
+                                                     linear_end=Y_.SCHEDULE["linear_end"]), 0.0, "eps")["lvlb_weights"].to(dev)
+    logvar = torch.full((lvlb.numel(),), -0.7, device=dev)
+    lv_m, lv_v = torch.zeros_like(logvar), torch.zeros_like(logvar)
+    full = dict(parameterization="eps", loss_type="l1", l_simple_weight=0.8, original_elbo_weight=10., logvar=logvar,
+                lvlb_weights=lvlb, learn_logvar=True)
     tr = UNetTrainer(unet, compute="bf16" if a.bf16 else "f32")
     n, c, hw = a.batch, ucfg["in_channels"], a.latent
     g = torch.Generator(device="cpu").manual_seed(0)
@@ -178,8 +191,10 @@ def main():
     loss_buf = torch.zeros(1, device=dev)
 
     def step():
-        loss = tr.p_losses(x0, ctx, t, noise, sa, sb, y=y)
+        loss = tr.p_losses(x0, ctx, t, noise, sa, sb, y=y, objective=full if a.objective == "full" else None)
         tr.adamw_step(lr=1e-6)
+        if a.objective == "full":
+            T.adamw_(logvar, tr.objective_out["dlogvar"], lv_m, lv_v, 1e-6, (0.9, 0.999), 1e-8, 1e-2, tr.P.step)
         tr.ema_update(shadow, 0.9999)
         loss_buf.copy_(loss)
 
@@ -205,6 +220,31 @@ def main():
         fwd_gemm = (42.17 if a.latent == 32 else 168.62) * 1e9 * n
         fwd_attn = (3.84 if a.latent == 32 else 61.43) * 1e9 * n
         res["step_tflops"] = round((3 * fwd_gemm + 3.5 * fwd_attn) / dt / 1e12, 1)
+    # the loss stage alone, over the output of one more forward pass, both forms in turn
+    tr.forward(x0, t, ctx, y=y)
+    co = noise.shape[1]
+
+    def stage_default():
+        tgt = torch.zeros_like(tr.eps_pad)
+        tgt[..., :co] = noise.permute(0, 2, 3, 1)
+        T.mse_grad(tr.eps_pad, tgt, denom=noise.numel())
+
+    def stage_full():
+        T.diffusion_loss(tr.eps_pad, noise, t, logvar, lvlb, "l1", 0.8, 10.)
+    us = dict(default=[], full=[])
+    for rnd_ in range(6):                   # (round 0 warms both up)
+        for name, fn in (("default", stage_default), ("full", stage_full)):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(200):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            if rnd_:
+                us[name].append(e0.elapsed_time(e1) / 200 * 1e3)
+    res.update(objective=a.objective, loss_stage_us_default=round(min(us["default"]), 1), loss_stage_us_full=round(min(us["full"]), 1),
+               loss_stage_us_default_max=round(max(us["default"]), 1), loss_stage_us_full_max=round(max(us["full"]), 1))
+    tr.tape, tr.G, tr.ginit, tr.last_pass = [], {}, set(), None
     res.update(loss=float(loss_buf.item()), peak_mem_gb=round(torch.cuda.max_memory_allocated() / 2 ** 30, 2))
     print(json.dumps(res))
 
