@@ -227,6 +227,16 @@ _SIGS = {
     "ldmk_diffusion_loss_scratch_elems": (C.c_longlong, [C.c_int]),
     "ldmk_diffusion_loss": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                       C.c_float, C.c_float, _fp, _fp]),
+    # ---- EncoderUNetModel's pooled heads and the classifier's cross-entropy
+    "ldmk_pool_mean": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
+    "ldmk_pool_mean_bwd": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
+    "ldmk_attnpool_tokens": (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_int, C.c_int, _fp]),
+    "ldmk_attnpool_tokens_bwd": (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
+    "ldmk_attnpool_fwd": (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
+    "ldmk_attnpool_bwd": (C.c_int, [_fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
+    "ldmk_cross_entropy": (C.c_int, [_fp, _fp, _fp, _fp, _fp, C.c_float, C.c_int, C.c_int, _fp]),
+    "ldmk_relu": (C.c_int, [_fp, _fp, C.c_longlong, _fp]),
+    "ldmk_relu_bwd": (C.c_int, [_fp, _fp, _fp, C.c_longlong, _fp]),
 }
 # every symbol include/ldmk.h declares (checked by tests/test_abi.py against the header text)
 EXPORTED = [k for k in _SIGS if k not in ("ldmk_igemm_force_config", "ldmk_attn_force_qt")]

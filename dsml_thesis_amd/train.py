@@ -197,7 +197,7 @@ class UNetTrainer:
         if u.num_classes is not None:        # forward order: emb = time_embed(t) + label_emb(y) comes before every block
             add("label_emb.weight", sd["label_emb.weight"])
         cin = u.in_channels
-        assert cin <= 32 and u.out_channels <= 32
+        assert cin <= 32
         add("in.wpad", ops.pack_conv3x3(F.pad(sd["input_blocks.0.0.weight"], (0, 0, 0, 0, 0, 32 - cin)).contiguous()))
         add("input_blocks.0.0.bias", sd["input_blocks.0.0.bias"])
         # the flat buffer follows the forward order of the layers: the backward finishes parameter gradients from the
@@ -238,6 +238,12 @@ class UNetTrainer:
                 add(prefix + "w", P[prefix + "w"])
                 bk = "op.bias" if m.kind == "down" else "conv.bias"
                 add(prefix + bk, sd[prefix + bk])
+        self._collect_head()
+
+    def _collect_head(self):
+        """The parameters past the last block, in forward order (EncoderUNetTrainer: the pooled head's)."""
+        u, sd, add = self.unet, self.unet._sd, self.P.add
+        assert u.out_channels <= 32
         for k in ("out.0.weight", "out.0.bias"):
             add(k, sd[k])
         add("out.wpad", ops.pack_conv3x3(F.pad(sd["out.2.weight"], (0, 0, 0, 0, 0, 0, 0, 32 - u.out_channels)).contiguous()))
@@ -599,6 +605,31 @@ class UNetTrainer:
         (L = 1: the shipped configs' fast path; 1 < L <= 128: general cross-attention; None for a UNet without spatial
         transformers), y (n,) class labels of a `num_classes` UNet.
         Returns eps (n,C_out,H,W); records the tape for backward()."""
+        u = self.unet
+        n, H, W_ = x.shape[0], x.shape[2], x.shape[3]
+        hs, hcur, ch_, cw_, run_layers = self._run_torso(x, timesteps, context, y)
+        for i, blk in enumerate(u.output_blocks):
+            skip, sh, sw = hs.pop()
+            assert (sh, sw) == (ch_, cw_)
+            hcur, ch_, cw_ = run_layers(f"output_blocks.{i}.", blk.layers, hcur, skip, ch_, cw_)
+        hw = ch_ * cw_
+        yo, so = self._gn(hcur, None, hw, "out.0.weight", "out.0.bias", 1e-5, True)
+        yo = yo.view(n, ch_, cw_, -1)
+        eps_pad = self._conv(yo, "out.wpad", "out.bpad", stats=False)
+        h_final = hcur
+
+        def bwd_out():
+            dyo = self._conv_bwd(self._take(eps_pad), yo, "out.wpad", "out.bpad")
+            self._gn_bwd(dyo.view(n * hw, -1), h_final, None, hw, so, "out.0.weight", "out.0.bias", True)
+        self._push(bwd_out, "out.0.weight")
+        self.eps_pad = eps_pad
+        self.last_pass = dict(tape=self.tape, G=self.G, ginit=self.ginit, eps_pad=eps_pad, dctx=self.dctx)
+        return eps_pad[..., :u.out_channels].permute(0, 3, 1, 2).contiguous()
+
+    def _run_torso(self, x, timesteps, context, y):
+        """The part of the forward a UNetModel and an EncoderUNetModel share: the time embedding, every ResBlock's emb_layers, the
+        input blocks and the middle block.  -> (hs: [(output, h, w)] of every input block, the middle block's output, its h, w,
+        run_layers: the walk over one block's layers, for the output blocks)."""
         u, p, dev = self.unet, self.P.p, self.dev
         T.set_compute(self.compute)
         if not x.is_cuda:
@@ -684,23 +715,7 @@ class UNetTrainer:
             hcur, ch_, cw_ = run_layers(f"input_blocks.{i}.", u.input_blocks[i].layers, hcur, None, ch_, cw_)
             hs.append((hcur, ch_, cw_))
         hcur, ch_, cw_ = run_layers("middle_block.", u.middle_block.layers, hcur, None, ch_, cw_)
-        for i, blk in enumerate(u.output_blocks):
-            skip, sh, sw = hs.pop()
-            assert (sh, sw) == (ch_, cw_)
-            hcur, ch_, cw_ = run_layers(f"output_blocks.{i}.", blk.layers, hcur, skip, ch_, cw_)
-        hw = ch_ * cw_
-        yo, so = self._gn(hcur, None, hw, "out.0.weight", "out.0.bias", 1e-5, True)
-        yo = yo.view(n, ch_, cw_, -1)
-        eps_pad = self._conv(yo, "out.wpad", "out.bpad", stats=False)
-        h_final = hcur
-
-        def bwd_out():
-            dyo = self._conv_bwd(self._take(eps_pad), yo, "out.wpad", "out.bpad")
-            self._gn_bwd(dyo.view(n * hw, -1), h_final, None, hw, so, "out.0.weight", "out.0.bias", True)
-        self._push(bwd_out, "out.0.weight")
-        self.eps_pad = eps_pad
-        self.last_pass = dict(tape=self.tape, G=self.G, ginit=self.ginit, eps_pad=eps_pad, dctx=self.dctx)
-        return eps_pad[..., :u.out_channels].permute(0, 3, 1, 2).contiguous()
+        return hs, hcur, ch_, cw_, run_layers
 
     def backward(self, deps_pad, pass_=None, reduce_world=1, bucket_elems=32 * 1024 * 1024):
         """deps_pad: gradient w.r.t. the channel-padded NHWC output (n,H,W,32) of the pass `pass_` (default: the last
@@ -836,6 +851,8 @@ class UNetTrainer:
                "ff1n": "ff.net.0.proj.weight"}
         mods = dict(u._walk())
         for name, wp in view.items():
+            if self._head_to_reference(name, wp, out):
+                continue
             if name in ("te0", "te2"):
                 out[f"time_embed.{name[2]}.weight"] = wp.t().contiguous()
             elif name in ("emb_all", "emb_all_b"):
@@ -884,6 +901,10 @@ class UNetTrainer:
                     out[name] = wp.clone()
         return out
 
+    def _head_to_reference(self, name, wp, out):
+        """Hook of state_dict_reference for parameters a subclass packs in layouts of its own; True: `name` is dealt with."""
+        return False
+
     def sync_to_module(self, flat=None):
         """Write the trained weights back into the wrapped UNetModel's nn.Parameters and re-pack its sampling program."""
         sd = self.state_dict_reference(flat)
@@ -914,6 +935,9 @@ def reference_grad_layout(unet, name, grads):
     (state-dict key -> tensor, e.g. from autograd on the oracle): what tests compare the HIP gradients against."""
     dev = next(iter(grads.values())).device
     cat = torch.cat
+    head = _encoder_head_layout(unet, name, grads)
+    if head is not None:
+        return head
     if name in ("te0", "te2"):
         return grads[f"time_embed.{name[2]}.weight"].t()
     if name == "emb_all":
@@ -954,3 +978,174 @@ def reference_grad_layout(unet, name, grads):
         b = name[:-3]
         return cat([grads[b + f"attn1.to_{c}.weight"] for c in "qkv"], 0).t()
     return grads[name]
+
+
+# ---- EncoderUNetModel (openaimodel.py:745-961): the shared torso + one of four pooled heads ------------------------------------
+_HEAD_FINAL = {"adaptive": "out.3.", "attention": "out.2.c_proj.", "spatial": "out.2.", "spatial_v2": "out.3."}   # the Linear to K
+
+
+def _rows_t(w):
+    """A reference Linear / 1x1 convolution weight [out][in][1...] -> the packed [in][out]."""
+    return w.reshape(w.shape[0], -1).t()
+
+
+def _encoder_head_layout(unet, name, grads):
+    """reference_grad_layout for the packed head parameters of an EncoderUNetModel; None: `name` is not one of them."""
+    pool = getattr(unet, "pool", None)
+    if pool is None or not name.startswith("out."):
+        return None
+    fk = _HEAD_FINAL[pool]
+    kp = (unet.out_channels + 31) // 32 * 32
+    if name == fk + "wpad":
+        return F.pad(_rows_t(grads[fk + "weight"]), (0, kp - unet.out_channels))
+    if name == fk + "bpad":
+        return F.pad(grads[fk + "bias"], (0, kp - unet.out_channels))
+    if name == "out.2.pos_t":
+        return grads["out.2.positional_embedding"].t()
+    if name == "out.2.pqkv":
+        return _rows_t(grads["out.2.qkv_proj.weight"])
+    if name == "out.0.lw":
+        return _rows_t(grads["out.0.weight"])
+    return None
+
+
+class EncoderUNetTrainer(UNetTrainer):
+    """Forward with a tape, backward, AdamW / EMA / all-reduce for an EncoderUNetModel.  The torso is UNetTrainer's; the heads run
+    on the kernels of csrc/classifier.hip (fp32 in both compute modes) and on `_lin` (which follows `compute`).  The Linear to
+    the K classes is kept zero-padded to a multiple of 32 columns (the GEMMs' channel granularity), like the UNet's out.wpad: the
+    pad columns see zero gradients and stay zero.  Packed names: `<final>.wpad / .bpad`, `out.2.pos_t` (positional_embedding
+    transposed to (T, C)), `out.2.pqkv` (qkv_proj, [C][3C], QKVAttention's own [q | k | v][head][d] columns), `out.0.lw`."""
+
+    def _collect_head(self):
+        u, sd, add = self.unet, self.unet._sd, self.P.add
+        K = u.out_channels
+        self.Kp = (K + 31) // 32 * 32
+        fk = self._final = _HEAD_FINAL[u.pool]
+        if u.pool in ("adaptive", "attention"):
+            if u.pool == "attention" and u.pool_d_head not in self.HEAD_WIDTHS:
+                raise NotImplementedError(f"EncoderUNetTrainer: AttentionPool2d heads of width {u.pool_d_head}")
+            for k in ("out.0.weight", "out.0.bias"):
+                add(k, sd[k])
+            if u.pool == "attention":
+                add("out.2.pos_t", sd["out.2.positional_embedding"].t().contiguous())
+                add("out.2.pqkv", _rows_t(sd["out.2.qkv_proj.weight"]).contiguous())
+                add("out.2.qkv_proj.bias", sd["out.2.qkv_proj.bias"])
+        else:
+            if u._feature_size % 32:
+                raise NotImplementedError(f"EncoderUNetTrainer: {u._feature_size} pooled features (a multiple of 32 is built)")
+            add("out.0.lw", _rows_t(sd["out.0.weight"]).contiguous())
+            add("out.0.bias", sd["out.0.bias"])
+            if u.pool == "spatial_v2":
+                for k in ("out.1.weight", "out.1.bias"):
+                    add(k, sd[k])
+        add(fk + "wpad", F.pad(_rows_t(sd[fk + "weight"]), (0, self.Kp - K)).contiguous())
+        add(fk + "bpad", F.pad(sd[fk + "bias"], (0, self.Kp - K)))
+
+    def _head_to_reference(self, name, wp, out):
+        u, fk = self.unet, self._final
+        if name == fk + "wpad":
+            out[fk + "weight"] = wp[:, :u.out_channels].t().contiguous().view(out[fk + "weight"].shape)
+        elif name == fk + "bpad":
+            out[fk + "bias"] = wp[:u.out_channels].clone()
+        elif name == "out.2.pos_t":
+            out["out.2.positional_embedding"] = wp.t().contiguous()
+        elif name == "out.2.pqkv":
+            out["out.2.qkv_proj.weight"] = wp.t().contiguous().view(out["out.2.qkv_proj.weight"].shape)
+        elif name == "out.0.lw":
+            out["out.0.weight"] = wp.t().contiguous()
+        else:
+            return False
+        return True
+
+    def sync_to_module(self, flat=None):
+        sd = self.state_dict_reference(flat)
+        with torch.no_grad():
+            for k, prm in self.unet.named_parameters():
+                prm.copy_(sd[k])
+
+    def forward(self, x, timesteps, keep_tape=True):
+        """x (n,C_in,H,W) fp32 NCHW, timesteps (n,) -> logits (n,K); records the tape for backward() unless keep_tape is False
+        (inference: the saved activations are dropped at once)."""
+        u = self.unet
+        n = x.shape[0]
+        hs, hcur, h, w, _ = self._run_torso(x, timesteps, None, None)
+        hw, fk, pool = h * w, self._final, u.pool
+        if pool == "adaptive":
+            # GN32 + SiLU -> AdaptiveAvgPool2d((1, 1)) -> 1x1 conv: on the (n, C) mean rows the conv is a Linear
+            yo, so = self._gn(hcur, None, hw, "out.0.weight", "out.0.bias", 1e-5, True)
+            feat = T.pool_mean(yo, n, hw)
+            logits = self._lin(feat, fk + "wpad", fk + "bpad", 1)
+
+            def bwd():
+                dfeat = self._lin_bwd(self._take(logits), feat, fk + "wpad", fk + "bpad")
+                dyo = T.pool_mean_bwd(dfeat, n, hw, feat.shape[1])
+                self._gn_bwd(dyo.view(n * hw, -1), hcur, None, hw, so, "out.0.weight", "out.0.bias", True)
+        elif pool == "attention":
+            # GN32 + SiLU -> AttentionPool2d (openaimodel.py:51-59); only token 0 leaves it, so only token 0's query is used
+            if hw + 1 != self.P.p["out.2.pos_t"].shape[0]:
+                raise L.LdmkError(f"EncoderUNetTrainer: pool='attention' was built for a {u.pool_grid}x{u.pool_grid} final grid, got {h}x{w}")
+            heads, d, Tk = u.pool_heads, u.pool_d_head, hw + 1
+            yo, so = self._gn(hcur, None, hw, "out.0.weight", "out.0.bias", 1e-5, True)
+            X = T.attnpool_tokens(yo, self.P.p["out.2.pos_t"], n, hw)
+            qkv = self._lin(X, "out.2.pqkv", "out.2.qkv_proj.bias", Tk)
+            att, probs = T.attnpool_fwd(qkv, n, Tk, heads, d)
+            logits = self._lin(att, fk + "wpad", fk + "bpad", 1)
+
+            def bwd():
+                datt = self._lin_bwd(self._take(logits), att, fk + "wpad", fk + "bpad")
+                dqkv = T.attnpool_bwd(qkv, probs, datt, n, Tk, heads, d)
+                dX = self._lin_bwd(dqkv, X, "out.2.pqkv", "out.2.qkv_proj.bias")
+                dyo, _ = T.attnpool_tokens_bwd(dX, n, hw, dpos_t=self.P.g["out.2.pos_t"], accumulate=self.acc_params)
+                self._gn_bwd(dyo, hcur, None, hw, so, "out.0.weight", "out.0.bias", True)
+        else:
+            # the H W mean of every input block's output (block 0's convolution included) and of the middle block's, side by side
+            feats = hs + [(hcur, h, w)]
+            fmat = torch.empty(n, u._feature_size, device=self.dev)
+            col = 0
+            for t_, fh, fw in feats:
+                T.pool_mean(t_, n, fh * fw, feat=fmat, col=col)
+                col += t_.shape[-1]
+            assert col == u._feature_size
+            z1 = self._lin(fmat, "out.0.lw", "out.0.bias", 1)
+            if pool == "spatial":
+                a1, s1 = T.relu(z1), None
+            else:                          # GroupNorm32 over (n, 2048): 32 groups of 64 channels, one "pixel"
+                a1, s1 = self._gn(z1, None, 1, "out.1.weight", "out.1.bias", 1e-5, True)
+            logits = self._lin(a1, fk + "wpad", fk + "bpad", 1)
+
+            def bwd():
+                da1 = self._lin_bwd(self._take(logits), a1, fk + "wpad", fk + "bpad")
+                if pool == "spatial":
+                    dz1 = T.relu_bwd(z1, da1)
+                else:
+                    self._gn_bwd(da1, z1, None, 1, s1, "out.1.weight", "out.1.bias", True)
+                    dz1 = self._take(z1)
+                dfm = self._lin_bwd(dz1, fmat, "out.0.lw", "out.0.bias")
+                c0 = 0
+                for t_, fh, fw in feats:       # a block output also carries (or will carry) its consumer's gradient
+                    g, acc = self._grad(t_)
+                    T.pool_mean_bwd(dfm, n, fh * fw, t_.shape[-1], col=c0, dx=g, accumulate=acc)
+                    c0 += t_.shape[-1]
+        self._push(bwd, "out.")
+        self.eps_pad = logits
+        out = logits[:, :u.out_channels].contiguous()
+        if keep_tape:
+            self.last_pass = dict(tape=self.tape, G=self.G, ginit=self.ginit, eps_pad=logits, dctx=None)
+        else:
+            self.tape, self.G, self.ginit, self._stats, self.last_pass = [], {}, set(), {}, None
+        return out
+
+    def backward(self, dlogits, pass_=None, reduce_world=1, bucket_elems=32 * 1024 * 1024):
+        """dlogits (n,K): gradient w.r.t. the logits of the pass `pass_` (default: the last forward).  Fills (or, with acc_params,
+        adds to) P.grad; returns d(loss)/d(x) (n,C_in,H,W) when want_dx."""
+        n, K = dlogits.shape
+        dl = torch.zeros(n, self.Kp, device=self.dev)
+        dl[:, :K] = dlogits
+        return super().backward(dl, pass_=pass_, reduce_world=reduce_world, bucket_elems=bucket_elems)
+
+    def classify_loss(self, x, t, y, reduce_world=1):
+        """forward + F.cross_entropy (mean) + backward: -> (mean loss [1], per-sample loss (n,), logits (n,K)); gradients in P.grad."""
+        logits = self.forward(x, t)
+        per, mean, dl = T.cross_entropy(logits, y.to(torch.int64).contiguous())
+        self.backward(dl, reduce_world=reduce_world)
+        return mean, per, logits

@@ -455,6 +455,121 @@ def gauss_kl_bwd(moments, noise=None, dz=None, w=0.0, dmoments=None):
     return dmoments
 
 
+# ---- EncoderUNetModel's pooled heads and the classifier's cross-entropy (csrc/classifier.hip): fp32 in both compute modes
+def pool_mean(x, n, hw, feat=None, col=0):
+    """Mean over the hw rows of an NHWC activation x (n, hw, c) (any shape with n*hw*c elements, c last) into columns
+    [col, col + c) of feat (n, ld); feat None: a fresh (n, c)."""
+    ops._chk(x, "pool_mean x")
+    c = x.shape[-1]
+    if x.numel() != n * hw * c:
+        raise ValueError(f"pool_mean: x {tuple(x.shape)} is not (n={n}, hw={hw}, c)")
+    feat = _f32(n, c, device=x.device) if feat is None else feat
+    ops._chk(feat, "pool_mean feat")
+    if feat.dim() != 2 or feat.shape[0] != n or col < 0 or col + c > feat.shape[1]:
+        raise ValueError(f"pool_mean: columns [{col}, {col + c}) of feat {tuple(feat.shape)} for n={n}")
+    L.call("ldmk_pool_mean", _ptr(x), _ptr(feat), n, hw, c, feat.shape[1], col, stream())
+    return feat
+
+
+def pool_mean_bwd(dfeat, n, hw, c, col=0, dx=None, accumulate=False):
+    """dx (n, hw, c) (+)= dfeat[:, col:col + c] / hw."""
+    ops._chk(dfeat, "pool_mean_bwd dfeat")
+    if dfeat.dim() != 2 or dfeat.shape[0] != n or col < 0 or col + c > dfeat.shape[1]:
+        raise ValueError(f"pool_mean_bwd: columns [{col}, {col + c}) of dfeat {tuple(dfeat.shape)} for n={n}")
+    if dx is None:
+        if accumulate:
+            raise ValueError("pool_mean_bwd: accumulate needs dx")
+        dx = _f32(n, hw, c, device=dfeat.device)
+    ops._chk(dx, "pool_mean_bwd dx")
+    if dx.numel() != n * hw * c:
+        raise ValueError(f"pool_mean_bwd: dx {tuple(dx.shape)} is not (n={n}, hw={hw}, c={c})")
+    L.call("ldmk_pool_mean_bwd", _ptr(dfeat), _ptr(dx), n, hw, c, dfeat.shape[1], col, 1 if accumulate else 0, stream())
+    return dx
+
+
+def attnpool_tokens(y, pos_t, n, hw):
+    """y (n*hw, c) rows, pos_t (hw + 1, c) -- the transpose of AttentionPool2d.positional_embedding -> X (n*(hw + 1), c)."""
+    ops._chk(y, "attnpool_tokens y")
+    ops._chk(pos_t, "attnpool_tokens pos_t")
+    c = y.shape[-1]
+    if y.numel() != n * hw * c or tuple(pos_t.shape) != (hw + 1, c):
+        raise ValueError(f"attnpool_tokens: y {tuple(y.shape)}, pos_t {tuple(pos_t.shape)} for n={n}, hw={hw}")
+    X = _f32(n * (hw + 1), c, device=y.device)
+    L.call("ldmk_attnpool_tokens", _ptr(y), _ptr(pos_t), _ptr(X), n, hw, c, stream())
+    return X
+
+
+def attnpool_tokens_bwd(dX, n, hw, dpos_t=None, accumulate=False, want_dy=True):
+    """dX (n*(hw + 1), c) -> (dy (n*hw, c), dpos_t (hw + 1, c) (+)= the sum over the samples, in sample order)."""
+    ops._chk(dX, "attnpool_tokens_bwd dX")
+    c = dX.shape[-1]
+    if dX.numel() != n * (hw + 1) * c:
+        raise ValueError(f"attnpool_tokens_bwd: dX {tuple(dX.shape)} for n={n}, hw={hw}")
+    if dpos_t is None:
+        if accumulate:
+            raise ValueError("attnpool_tokens_bwd: accumulate needs dpos_t")
+        dpos_t = _f32(hw + 1, c, device=dX.device)
+    ops._chk(dpos_t, "attnpool_tokens_bwd dpos_t")
+    if dpos_t.numel() != (hw + 1) * c:
+        raise ValueError(f"attnpool_tokens_bwd: dpos_t {tuple(dpos_t.shape)} for hw={hw}, c={c}")
+    dy = _f32(n * hw, c, device=dX.device) if want_dy else None
+    L.call("ldmk_attnpool_tokens_bwd", _ptr(dX), _ptr(dy), _ptr(dpos_t), n, hw, c, 1 if accumulate else 0, stream())
+    return dy, dpos_t
+
+
+def attnpool_fwd(qkv, n, tokens, heads, d_head):
+    """Single-query attention of AttentionPool2d: qkv (n*tokens, 3*heads*d_head), columns [q | k | v][head][d] ->
+    (out (n, heads*d_head): token 0's attention output, probs (n, heads, tokens) for the backward)."""
+    ops._chk(qkv, "attnpool_fwd qkv")
+    C_ = heads * d_head
+    if qkv.numel() != n * tokens * 3 * C_:
+        raise ValueError(f"attnpool_fwd: qkv {tuple(qkv.shape)} for n={n}, tokens={tokens}, heads={heads}, d_head={d_head}")
+    out, probs = _f32(n, C_, device=qkv.device), _f32(n, heads, tokens, device=qkv.device)
+    L.call("ldmk_attnpool_fwd", _ptr(qkv), _ptr(out), _ptr(probs), n, tokens, heads, int(d_head), stream())
+    return out, probs
+
+
+def attnpool_bwd(qkv, probs, dout, n, tokens, heads, d_head):
+    """-> dqkv shaped like qkv, every element written (zeros in the q columns of the tokens past the first)."""
+    for name, t in (("qkv", qkv), ("probs", probs), ("dout", dout)):
+        ops._chk(t, f"attnpool_bwd {name}")
+    C_ = heads * d_head
+    if qkv.numel() != n * tokens * 3 * C_ or probs.numel() != n * heads * tokens or dout.numel() != n * C_:
+        raise ValueError(f"attnpool_bwd: qkv {tuple(qkv.shape)}, probs {tuple(probs.shape)}, dout {tuple(dout.shape)} for n={n}, "
+                         f"tokens={tokens}, heads={heads}, d_head={d_head}")
+    dqkv = torch.empty_like(qkv)
+    L.call("ldmk_attnpool_bwd", _ptr(qkv), _ptr(probs), _ptr(dout), _ptr(dqkv), n, tokens, heads, int(d_head), stream())
+    return dqkv
+
+
+def cross_entropy(logits, target, scale=None, want_dlogits=True):
+    """F.cross_entropy of logits (n, K), 1 <= K <= 1024, against int64 targets (n,): -> (per-sample loss (n,), mean loss [1],
+    dlogits = (softmax - onehot) * scale or None).  scale None: 1 / n, the gradient of the mean."""
+    ops._chk(logits, "cross_entropy logits")
+    if logits.dim() != 2 or not 1 <= logits.shape[1] <= 1024:
+        raise ValueError(f"cross_entropy: logits {tuple(logits.shape)}: (n, K) with 1 <= K <= 1024")
+    n, K = logits.shape
+    if not (target.is_cuda and target.is_contiguous()) or target.dtype != torch.int64 or target.numel() != n:
+        raise ValueError(f"cross_entropy: targets {target.dtype} {tuple(target.shape)}: contiguous int64 CUDA, one per row of the logits")
+    per, mean = _f32(n, device=logits.device), _f32(1, device=logits.device)
+    dl = torch.empty_like(logits) if want_dlogits else None
+    L.call("ldmk_cross_entropy", _ptr(logits), _ptr(target), _ptr(per), _ptr(mean), _ptr(dl), float(1.0 / n if scale is None else scale),
+           n, K, stream())
+    return per, mean, dl
+
+
+def relu(x, out=None):
+    out = torch.empty_like(x) if out is None else out
+    L.call("ldmk_relu", _ptr(x), _ptr(out), x.numel(), stream())
+    return out
+
+
+def relu_bwd(x, dy, out=None):
+    out = torch.empty_like(x) if out is None else out
+    L.call("ldmk_relu_bwd", _ptr(x), _ptr(dy), _ptr(out), x.numel(), stream())
+    return out
+
+
 def adamw_(p, g, m, v, lr, betas, eps, weight_decay, step):
     L.call("ldmk_adamw", _ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), lr, betas[0], betas[1], eps, weight_decay, step, stream())
 

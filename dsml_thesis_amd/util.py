@@ -26,6 +26,8 @@ TARGET_MAP = {
     "ldm.modules.encoders.modules.Conv1DTemporalAttention": "dsml_thesis_amd.encoders.Conv1DTemporalAttention",
     "ldm.models.diffusion.ddim.DDIMSampler": "dsml_thesis_amd.ddim.DDIMSampler",
     "ldm.models.diffusion.ddim2cond.DDIMSampler": "dsml_thesis_amd.ddim.DDIMSampler",
+    "ldm.modules.diffusionmodules.openaimodel.EncoderUNetModel": "dsml_thesis_amd.encoder_unet.EncoderUNetModel",
+    "ldm.models.diffusion.classifier.NoisyLatentImageClassifier": "dsml_thesis_amd.classifier.NoisyLatentImageClassifier",
 }
 
 

@@ -878,6 +878,38 @@ int ldmk_diffusion_loss(const float* pred, const float* target, const long long*
                         const float* lvlb_weights, float* dpred, float* dlogvar, float* scalars, float* ls, int n, int c, int hw,
                         int T, int loss_type, float l_simple_weight, float original_elbo_weight, double* scratch, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The pooled heads of EncoderUNetModel (openaimodel.py:751-961) and the classifier's cross-entropy (csrc/classifier.hip); the
+ * conventions of the kernels above: fp32 in and out, no float atomics, every sum in double in one fixed order, bitwise reproducible.
+ * Spatial mean of an NHWC activation x (n, hw, c) into columns [col, col + c) of a row-major feature matrix feat (n, ld), and its
+ * backward dx[b][i][k] (+)= dfeat[b][col + k] / hw (accumulate != 0: added to dx).  0 <= col, col + c <= ld. */
+int ldmk_pool_mean(const float* x, float* feat, int n, int hw, int c, int ld, int col, void* stream);
+int ldmk_pool_mean_bwd(const float* dfeat, float* dx, int n, int hw, int c, int ld, int col, int accumulate, void* stream);
+/* Token rows of AttentionPool2d (openaimodel.py:30-58), T = hw + 1: X (n, T, c) from y (n, hw, c) and the positional embedding
+ * pos_t (T, c) -- the TRANSPOSE of the reference's (c, T) parameter, the layout the trainer keeps it in:
+ *   X[b][0] = mean_i y[b][i] + pos_t[0];   X[b][i + 1] = y[b][i] + pos_t[i + 1]
+ * Backward: dy[b][i] = dX[b][i + 1] + dX[b][0] / hw;  dpos_t[t] (+)= sum_b dX[b][t] in sample order (acc_dpos != 0: added).
+ * dy or dpos_t may be NULL. */
+int ldmk_attnpool_tokens(const float* y, const float* pos_t, float* X, int n, int hw, int c, void* stream);
+int ldmk_attnpool_tokens_bwd(const float* dX, float* dy, float* dpos_t, int n, int hw, int c, int acc_dpos, void* stream);
+/* Single-query attention of AttentionPool2d: only token 0's output is used, so only its query is.  qkv (n, T, 3C), C = heads *
+ * d_head, columns [q | k | v][head][d] (QKVAttention's order, which is qkv_proj's own row order).  Per (sample, head), one wave:
+ *   s_t = (q_0 . k_t) d_head^-1/2;  p = softmax_t(s) (max-subtracted, fp32);  out (n, C)[head] = sum_t p_t v_t
+ * probs (n, heads, T) keeps p for the backward, which writes ALL of dqkv (n, T, 3C):
+ *   dv_t = p_t dout;  ds_t = p_t (dout . v_t - sum_u p_u dout . v_u);  dq_0 = d^-1/2 sum_t ds_t k_t;  dk_t = d^-1/2 ds_t q_0
+ * and zeros in the q columns of every token but 0.  d_head % 4 == 0, 4 <= d_head <= 128; 1 <= T <= 4096; qkv 16-byte aligned. */
+int ldmk_attnpool_fwd(const float* qkv, float* out, float* probs, int n, int T, int heads, int d_head, void* stream);
+int ldmk_attnpool_bwd(const float* qkv, const float* probs, const float* dout, float* dqkv, int n, int T, int heads, int d_head,
+                      void* stream);
+/* Softmax cross-entropy, F.cross_entropy without ignore_index or label smoothing: logits (n, K), 1 <= K <= 1024, target int64 [n]
+ * (clamped into [0, K)).  per_sample[b] = logsumexp(logits[b]) - logits[b][target[b]] (reduction='none'), mean[0] their mean in
+ * sample order, dlogits (n, K) = (softmax - onehot) * scale (NULL: skipped).  Max-subtracted. */
+int ldmk_cross_entropy(const float* logits, const long long* target, float* per_sample, float* mean, float* dlogits, float scale,
+                       int n, int K, void* stream);
+/* y = max(x, 0);  dx = x > 0 ? dy : 0 */
+int ldmk_relu(const float* x, float* y, long long n, void* stream);
+int ldmk_relu_bwd(const float* x, const float* dy, float* dx, long long n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
