@@ -148,6 +148,10 @@ _SIGS = {
                                  _fp, _fp, C.c_int, C.c_int, C.c_int, _fp]),
     "ldmk_dpm_step": (C.c_int, [_fp, _fp, _fp, _fp, C.c_float, C.c_int, _fp, _fp, _fp, C.c_longlong, C.c_int, _fp, C.c_int, C.c_int,
                                 C.c_int, C.c_int, _fp]),
+    "ldmk_dpm_stage": (C.c_int, [_fp, _fp, _fp, _fp, C.c_float, C.c_int, _fp, _fp, _fp, _fp, _fp, _fp, C.c_longlong, C.c_int, _fp,
+                                 C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
+    "ldmk_dpm_predict_x0": (C.c_int, [_fp, _fp, _fp, _fp, C.c_float, C.c_int, _fp, C.c_longlong, C.c_int, C.c_int, _fp]),
+    "ldmk_abs_quantile_rows": (C.c_int, [_fp, C.c_int, C.c_longlong, C.c_float, C.c_float, _fp, _fp]),
     "ldmk_advance_timestep": (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_int, C.c_int, _fp]),
     "ldmk_ddpm_step": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_longlong, C.c_int, _fp]),
     "ldmk_patch_unfold": (C.c_int, [_fp, _fp] + [C.c_int] * 10 + [_fp]),

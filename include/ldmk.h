@@ -575,6 +575,47 @@ int ldmk_plms_step(const float* x, const float* eps, const float* table, int* st
 int ldmk_dpm_step(const float* x, const float* eps, const float* table, int* step_idx, float cfg_scale, int cfg, float* hist,
                   float* x_prev, float* pred_x0, long long per_sample, int n, float* ts, int n_ts, int advance, int n_steps,
                   int max_order, void* stream);
+/* ldmk_dpm_stage: the update after ONE model evaluation of `DPM_Solver.sample` (csrc/dpm.hip; dpm_solver.py:504-857): singlestep
+ *   and multistep, data-prediction (x0) and noise-prediction (eps) form, solver types 'dpm_solver' and 'taylor', thresholded or not.
+ *   table: [n_rows][16] float32, one row per model evaluation, made on the host (dsml_thesis_amd.dpm_solver.method_table):
+ *     0 alpha, 1 sigma at the evaluation's time   2 kind   3 c_x   4 c_0   5..12 per kind (below)   13 unused
+ *     14 flags: 1 = x0 form (m = (x - sigma e) / alpha; else m = e), 2 = m is thresholded   15 the model time of the NEXT row
+ *   step_idx: device int32, the CURRENT row k (read clamped to [0, n_rows - 1]).  Per element e = e_u + scale (e_c - e_u) when cfg
+ *   (eps = [uncond | cond], 2n items), then m as the flags say; under flag 2 m = clamp(x0_pre, -s, s) / s with s = s[item] and
+ *   x0_pre the unthresholded data prediction (ldmk_dpm_predict_x0, ldmk_abs_quantile_rows).  m goes to model_out (may be NULL).
+ *   With x_s, m_s, m_s1 the three slots of `keep` [3][n * per_sample] and m1, m2 the ring's entries of rows k-1, k-2:
+ *     kind 0  singlestep, stage 0:         x' = c_x x - c_0 m;  x_s = x, m_s = m
+ *     kind 1  singlestep order 3, stage 1: x' = (c_x x_s - c_0 m_s) + [5] (m - m_s);  m_s1 = m
+ *     kind 2  singlestep, last stage:      x' = (c_x x_s - c_0 m_s) + [5] (m - m_s)
+ *     kind 3  singlestep order 3 'taylor', last stage: [5] 1/r1  [6] 1/r2  [7] r1  [8] r2  [9] c_1  [10] c_2  [11] r2 - r1
+ *             D1_0 = [5] (m_s1 - m_s), D1_1 = [6] (m - m_s), D1 = ([8] D1_0 - [7] D1_1) / [11], D2 = 2 (D1_1 - D1_0) / [11];
+ *             x' = ((c_x x_s - c_0 m_s) + c_1 D1) - c_2 D2
+ *     kind 4  multistep order 1: x' = c_x x - c_0 m
+ *     kind 5  multistep order 2: [5] 1/r0  [9] c_1;  x' = (c_x x - c_0 m) + c_1 ([5] (m - m1))
+ *     kind 6  multistep order 3: [5] 1/r0  [6] 1/r1  [7] r0 / (r0 + r1)  [8] 1 / (r0 + r1)  [9] c_1  [10] c_2;  D1_0, D1_1, D1, D2 as
+ *             ldmk_dpm_step forms them;  x' = ((c_x x - c_0 m) + c_1 D1) - c_2 D2
+ *     kind 7  denoise_to_zero: x' = m
+ *   The host folds the reference's sign and its scalar factors into [5] and c_1 (x - k d == x + (-k) d bit for bit), so one row
+ *   layout serves both forms and both solver types.  fp32, every operation rounded on its own, in the order written.  x_prev may be
+ *   x.  Kinds 4-6 write m to ring slot k % 3 (hist: [3][n * per_sample], as ldmk_dpm_step).  A kind-0 row reads neither keep nor hist.
+ *   uses: bit 0 = the table has kinds 0-3 (keep required), bit 1 = kinds 4-6 (hist required); a row whose kind `uses` does not
+ *   allow writes NaN to x' and touches nothing else.  thresholded rows need x0_pre and s.
+ *   advance is 0 or 1: ts[0..n_ts) = row k's [15], then step_idx = k + 1.  No atomics: results are bitwise reproducible. */
+int ldmk_dpm_stage(const float* x, const float* eps, const float* table, int* step_idx, float cfg_scale, int cfg,
+                   const float* x0_pre, const float* s, float* keep, float* hist, float* x_prev, float* model_out,
+                   long long per_sample, int n, float* ts, int n_ts, int advance, int n_rows, int uses, void* stream);
+/* the unthresholded data prediction of row k, x0 = (x - sigma e) / alpha with e combined as above (dpm_solver.py:390-393) */
+int ldmk_dpm_predict_x0(const float* x, const float* eps, const float* table, const int* step_idx, float cfg_scale, int cfg,
+                        float* x0, long long per_sample, int n, int n_rows, void* stream);
+/* ldmk_abs_quantile_rows: s_out[r] = max(quantile(|v[r, 0..per)|, q), floor_val), bit for bit torch.quantile(v.abs(), q, dim=1) on
+ *   the CPU (linear interpolation) followed by torch.maximum (dpm_solver.py:396-397):
+ *     rank = fl32(q (per - 1)), lo = floor(rank), hi = ceil(rank), w = rank - lo, a and b the order statistics at ranks lo and hi,
+ *     result = w < 0.5 ? fma(w, b - a, a) : fma(-(b - a), 1 - w, b): b - a and 1 - w rounded on their own, each branch ONE fused
+     multiply-add, which is how torch's lerp rounds on the CPU (a product rounded on its own differs in the last bit now and then).
+ *   A row holding a NaN gives NaN, and so does one whose a or b is inf (inf - inf).  One workgroup per row: an exact radix select
+ *   over the bit patterns of |v| with integer histograms in LDS, then the next larger key when hi's statistic is not a's.  No float
+ *   atomics: bitwise reproducible.  0 <= q <= 1, 1 <= per <= 2^20 (larger is refused). */
+int ldmk_abs_quantile_rows(const float* v, int rows, long long per, float q, float floor_val, float* s_out, void* stream);
 /* the counter/timestep advance of ldmk_ddim_step on its own (used by the ancestral loop): index -= advance,
  * clamped to [0, n_steps-1]; ts[0..n_ts) = timesteps[index] */
 int ldmk_advance_timestep(int* step_idx, const long long* timesteps, long long* ts, int n_ts, int advance, int n_steps,
