@@ -1305,10 +1305,11 @@ constexpr int kNumSCfg = 8;
 const char* igemm_ws_unsupported(const ldmk_igemm_args& a, int wcfg, int splitk);
 int igemm_ws_dispatch(const ldmk_igemm_args& a, int wcfg, int splitk, float* ws, hipStream_t st);
 constexpr int kNumWCfg = 2;
-// the pre-split bf16x3 tiles (igemm_ps.hip): tile_cfg kNumCfg+kNumRCfg+kNumSCfg+kNumWCfg+1 .. +6
+// the pre-split tiles (igemm_ps.hip): tile_cfg kNumCfg+kNumRCfg+kNumSCfg+kNumWCfg+1 .. +13 (23..35), then the same 13 bases with two
+// K groups inside the workgroup (36..48; 40 = 27's and 48 = 35's run, the others are refused with their reason)
 const char* igemm_ps_unsupported(const ldmk_igemm_args& a, int pcfg, int splitk);
 int igemm_ps_dispatch(const ldmk_igemm_args& a, int pcfg, int splitk, float* ws, hipStream_t st);
-constexpr int kNumPCfg = 11;
+constexpr int kNumPCfg = 26;
 
 }  // namespace ldmk
 
@@ -1433,7 +1434,7 @@ static int igemm_entry(const ldmk_igemm_args* args, void* stream, bool launch) {
   }
   if (a.compute == LDMK_COMPUTE_F16X2) {
     LDMK_REQUIRE(a.tile_cfg <= kNumCfg || ps_tile, "ldmk_igemm: LDMK_COMPUTE_F16X2 runs on the LDS-tiled shapes (tile_cfg 0..6) and the pre-split "
-                 "tiles (23..28, 31..33), not tile_cfg=%d", a.tile_cfg);
+                 "tiles (23..28, 31..35, 40, 48), not tile_cfg=%d", a.tile_cfg);
     LDMK_REQUIRE(!a.a_split && a.w_scale_exp >= -60 && a.w_scale_exp <= 60, "ldmk_igemm: LDMK_COMPUTE_F16X2: a_split is not taken; w_scale_exp=%d", a.w_scale_exp);
     if (!ps_tile) {
       LDMK_REQUIRE(a.w_split && !a.b_trans && a.w_split_ld >= a.K && a.w_split_ld % 8 == 0 && 2LL * a.N * a.w_split_ld * 2 < (1LL << 32),

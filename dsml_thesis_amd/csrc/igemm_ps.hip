@@ -103,7 +103,8 @@ constexpr int PS_KV_TILE = 16 * 1024;          // = H2_TILE of csrc/attention_bf
 // 64 outputs per lane, a third of them addressing and predication.  Lane = column form (the convolutions: bias, then the
 // time-embedding vector or the skip connection, GroupNorm records): col_lean of csrc/ldmk_epilogue.h.  Same arithmetic, rounding
 // by rounding, as the general form (0).
-template <int TM, int TN, bool TR, int PL = 3, bool KV = false, int LEAN = 0>
+// ROWREC (the K groups, KG = 2): GroupNorm records in the row order of the split-K reduce launch (gn_tile_record_rows).
+template <int TM, int TN, bool TR, int PL = 3, bool KV = false, int LEAN = 0, bool ROWREC = false>
 __device__ __forceinline__ void ps_epilogue(const ldmk_igemm_args& p, f32x16 (&acc)[TM][TN], const int rowbase, const int colbase,
                                             const int splitk, const int ks, const int bz, float* __restrict__ ws, const int lane,
                                             float* __restrict__ kv_ts = nullptr) {
@@ -332,8 +333,8 @@ __device__ __forceinline__ void ps_epilogue(const ldmk_igemm_args& p, f32x16 (&a
       return;
     }
     // (dispatch, col_lean_form: whole wave tile inside M x N, no split-K, no folded LayerNorm, 32-row tiles inside one sample)
-    if constexpr (LEAN != 0) col_lean<TM, TN, LEAN>(p, acc, rowbase, colbase, bz, l31, half);
-    else col_general<TM, TN>(p, acc, rowbase, colbase, bz, l31, half, lnf);
+    if constexpr (LEAN != 0) col_lean<TM, TN, LEAN, ROWREC>(p, acc, rowbase, colbase, bz, l31, half);
+    else col_general<TM, TN, ROWREC>(p, acc, rowbase, colbase, bz, l31, half, lnf);
   }
 }
 
@@ -351,19 +352,73 @@ __device__ __forceinline__ int ps_lean_form(const ldmk_igemm_args& p, const int 
   }
 }
 
-template <int NWM, int NWN, int TM, int TN, int NS, bool TR, int PL = 3, bool KV = false>
-__global__ __launch_bounds__(64 * NWM * NWN, 2) void igemm_ps_kernel(const ldmk_igemm_args p, const int splitk, float* __restrict__ ws, const int dbg_arg, const int nfast) {
+// K groups (KG = 2 of igemm_ps_kernel / igemm_psc_kernel), the hand-over after the main loop; true = this wave is done (group 1).
+// Barrier 1: every wave has waited for its own DMAs (wait_vm<0> before the call) and issued its last fragment reads, whose values
+// its matrix instructions have consumed -- both rings are dead memory.  Group 1 stores its accumulators there (wave w: 4 CH KiB at
+// w x that; one KiB per (tile, q) with lane l at 16 l: ds_write_b128, conflict-free); __syncthreads waits for the LDS counter
+// before barrier 2, after which group 0 reads the same addresses and forms acc0 + acc1.  CH = the 32x32 tiles per wave that fit
+// the two rings at a time: a wider wave tile (32 x 320: ten tiles, seven fit) goes over in passes, the next pass's barrier 1
+// coming after group 0's reads of this one.  (The fused-QKV form keeps group 1 to the barrier that frees this memory for the V^T
+// scratch.)
+template <int TM, int TN, int CH, bool KV>
+__device__ __forceinline__ bool ps_kgroup_combine(f32x16 (&acc)[TM][TN], unsigned char* smem, const int wave, const unsigned lane16, const int grp) {
+  float4* xch = reinterpret_cast<float4*>(smem + wave * (CH * 4096) + lane16);
+#pragma unroll
+  for (int t0 = 0; t0 < TM * TN; t0 += CH) {
+    __syncthreads();
+    if (grp == 1) {
+#pragma unroll
+      for (int t = t0; t < t0 + CH && t < TM * TN; ++t)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const f32x16& a = acc[t / TN][t % TN];
+          xch[((t - t0) * 4 + q) * 64] = make_float4(a[4 * q], a[4 * q + 1], a[4 * q + 2], a[4 * q + 3]);
+        }
+    }
+    __syncthreads();
+    if (grp == 0) {
+#pragma unroll
+      for (int t = t0; t < t0 + CH && t < TM * TN; ++t)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const float4 v = xch[((t - t0) * 4 + q) * 64];
+          f32x16& a = acc[t / TN][t % TN];
+          a[4 * q] += v.x; a[4 * q + 1] += v.y; a[4 * q + 2] += v.z; a[4 * q + 3] += v.w;
+        }
+    }
+  }
+  if (grp == 1) {
+    if constexpr (KV) __syncthreads();
+    return true;
+  }
+  return false;
+}
+
+// K groups inside the workgroup (KG = 2, four-wave tiles only: tile_cfg 40 / 48): the workgroup runs 2 NW waves, wave = (group, wm, wn);
+// each group owns a ring of its own and the K slice that splitk = 2 would give it (the same it_per partition in 32-deep chunks),
+// both run the stage count of the longer slice -- the shorter one through the out-of-range zero stages every launch ends with --
+// so the one s_barrier per stage stays workgroup-wide and in lockstep, and a wave still counts only its own DMAs.  After the
+// loop group 1 hands its accumulators over through the (then free) ring memory, group 0 forms acc0 + acc1 -- the sum
+// 0 + s0 + s1 of the reduce launch, bit for bit -- and runs the ordinary epilogue: every epilogue, also those the split over
+// workgroups cannot run (GEGLU, out_ps, attn_kv_out).  A second wave per SIMD for the rows that fill the chip with one
+// four-wave workgroup per CU, without the slab round trip and the second launch.
+template <int NWM, int NWN, int TM, int TN, int NS, bool TR, int PL = 3, bool KV = false, int KG = 1>
+__global__ __launch_bounds__(64 * NWM * NWN * KG, KG == 1 ? 2 : 1) void igemm_ps_kernel(const ldmk_igemm_args p, const int splitk, float* __restrict__ ws, const int dbg_arg, const int nfast) {
   const int dbg = PS_PROBES ? dbg_arg : 0;        // (what-if switches: probe builds only, see PS_PROBES)
   constexpr int NW = NWM * NWN;
+  static_assert(KG == 1 || (KG == 2 && NW == 4), "K groups: two groups of a four-wave tile");
   constexpr int BM = 32 * TM * NWM, BN = 32 * TN * NWN;
   constexpr int FA = BM / 32, FB = BN / 32, U = FA + FB;          // units (3-plane blocks) per stage
   constexpr int UHI = (U + NW - 1) / NW, ULO = U / NW;            // units a wave fetches per stage
   constexpr int UB = PL * 1024;                                     // bytes per unit
   constexpr int STAGE = U * UB;                                     // bytes
   static_assert(PL * UHI * (NS - 1) <= 63, "vmcnt is a 6-bit counter");
-  extern __shared__ __attribute__((aligned(1024))) unsigned char smem_ps[];      // [NS][STAGE]
+  constexpr int XFIT = NS * STAGE * KG / (NW * 4096), XCH = KG == 1 ? 1 : (TM * TN < XFIT ? TM * TN : XFIT);      // 32x32 tiles per wave and hand-over pass
+  static_assert(XCH >= 1, "the hand-over of group 1's accumulators needs room for a tile per wave");
+  extern __shared__ __attribute__((aligned(1024))) unsigned char smem_ps[];      // [KG][NS][STAGE]
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int tid = threadIdx.x, lane = tid & 63, wave_all = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int grp = KG == 1 ? 0 : wave_all / NW, wave = wave_all - grp * NW;       // (K group, wave within the group)
   const int l31 = lane & 31, half = lane >> 5;
   const int wm = wave / NWN, wn = wave - wm * NWN;
 
@@ -377,11 +432,13 @@ __global__ __launch_bounds__(64 * NWM * NWN, 2) void igemm_ps_kernel(const ldmk_
   const int n0 = (nfast & 1) ? (bid % tiles_n) * BN : (bid / tiles_m) * BN;
   const int ks = blockIdx.y, bz = blockIdx.z;
 
+  // (KG = 2: splitk == 1, the host refuses anything else; group g takes slice g of the two-way partition)
   const int nkc = p.K / 32;
-  const int it_per = (nkc + splitk - 1) / splitk;
-  const int it_begin = ks * it_per;
+  const int it_per = KG == 1 ? (nkc + splitk - 1) / splitk : (nkc + KG - 1) / KG;
+  const int it_begin = (KG == 1 ? ks : grp) * it_per;
   const int it_end = min(nkc, it_begin + it_per);
   const int n16 = it_end > it_begin ? 2 * (it_end - it_begin) : 0;
+  const int n16_wg = KG == 1 ? n16 : 2 * min(nkc, it_per);       // stages every wave of the workgroup runs (slice 0 is the longest)
   const int Kb = p.K / 16;
   const int Mb = (p.M + 31) / 32, Nb = p.N / 32;
 
@@ -389,9 +446,11 @@ __global__ __launch_bounds__(64 * NWM * NWN, 2) void igemm_ps_kernel(const ldmk_
   //  no memory traffic; bit 1 = no DMA instructions at all; bit 2 = no matrix instructions.  Results are garbage then.)
   // Two A sources (args.a_ps1): k-slabs [0, Ka0) of A come from a_ps, a PS tensor of its own K-width a_ps_k0, slabs [Ka0, Kb) from
   // a_ps1 (width K - a_ps_k0) -- the K-concat [A0 | A1] without a tensor that holds it.  One source: Ka0 = Kb, rs_a1 is never read.
-  const int Ka0 = p.a_ps1 ? p.a_ps_k0 / 16 : Kb, Ka1 = Kb - Ka0;
+  // (SRC2: the 128x320 tile with K groups takes one source only -- the host refuses a_ps1 there: its scalar registers are full)
+  constexpr bool SRC2 = !(KG == 2 && TN == 10);
+  const int Ka0 = (SRC2 && p.a_ps1) ? p.a_ps_k0 / 16 : Kb, Ka1 = Kb - Ka0;
   const u32x4 rs_a = buffer_rsrc(reinterpret_cast<const unsigned char*>(p.a_ps) + (long long)bz * p.a_ps_bstride, (dbg & 1) ? 0u : (unsigned)Mb * (unsigned)Ka0 * (unsigned)UB);
-  const u32x4 rs_a1 = buffer_rsrc(p.a_ps1 ? p.a_ps1 : p.a_ps, (dbg & 1) ? 0u : (unsigned)Mb * (unsigned)Ka1 * (unsigned)UB);
+  const u32x4 rs_a1 = SRC2 ? buffer_rsrc(p.a_ps1 ? p.a_ps1 : p.a_ps, (dbg & 1) ? 0u : (unsigned)Mb * (unsigned)Ka1 * (unsigned)UB) : rs_a;
   const u32x4 rs_b = buffer_rsrc(reinterpret_cast<const unsigned char*>(p.w_ps) + (long long)bz * p.w_ps_bstride, (dbg & 1) ? 0u : (unsigned)Nb * (unsigned)Kb * (unsigned)UB);
   // this wave's units u = wave + NW i: byte offset of the block's first k-slab (wave-uniform), or PS_OOB for blocks past the edge;
   // ubase1: the same for an A unit in the second source, so that ubase1 + s UB is the offset of global slab 2 it_begin + s there
@@ -406,11 +465,12 @@ __global__ __launch_bounds__(64 * NWM * NWN, 2) void igemm_ps_kernel(const ldmk_
     ubase1[i] = (unsigned)blk * (unsigned)Ka1 * (unsigned)UB + (unsigned)(2 * it_begin - Ka0) * (unsigned)UB;
   }
   const unsigned lane16 = lane * 16;
-  const unsigned lds0 = (unsigned)(size_t)smem_ps;
+  unsigned char* const ring = smem_ps + grp * (NS * STAGE);      // this group's ring
+  const unsigned lds0 = (unsigned)(size_t)ring;
   auto issue = [&](int s) {                     // the DMA of local stage s into ring buffer s % NS (stages past the end: zeros)
     const unsigned buf = lds0 + (unsigned)(s % NS) * STAGE;
     const bool live = s < n16;
-    const bool src1 = 2 * it_begin + s >= Ka0;  // (wave-uniform: this stage's A slab lies in the second source)
+    const bool src1 = SRC2 && 2 * it_begin + s >= Ka0;  // (wave-uniform: this stage's A slab lies in the second source)
     const u32x4 rs_as = src1 ? rs_a1 : rs_a;
 #pragma unroll
     for (int i = 0; i < UHI; ++i) {
@@ -445,13 +505,13 @@ __global__ __launch_bounds__(64 * NWM * NWN, 2) void igemm_ps_kernel(const ldmk_
   }
 #pragma unroll
   for (int s = 0; s < NS - 1; ++s) issue(s);
-  for (int it = 0; it < n16; ++it) {
+  for (int it = 0; it < n16_wg; ++it) {
     // stage `it` of THIS wave has landed when all but the (NS - 2) younger stages' loads are done; the barrier then makes
     // every wave's part visible and certifies that buffer (it - 1) % NS is no longer read
     if (hi_wave) wait_vm<PL * UHI * (NS - 2)>(); else wait_vm<PL * ULO * (NS - 2)>();
     asm volatile("s_barrier" ::: "memory");
     issue(it + NS - 1);
-    const unsigned char* sb = smem_ps + (it % NS) * STAGE + lane16;
+    const unsigned char* sb = ring + (it % NS) * STAGE + lane16;
     bf16x8 a8[PL][TM];
 #pragma unroll
     for (int g = 0; g < PL; ++g)
@@ -503,6 +563,9 @@ __global__ __launch_bounds__(64 * NWM * NWN, 2) void igemm_ps_kernel(const ldmk_
     }
   }
   wait_vm<0>();             // (the trailing out-of-range loads still target this workgroup's LDS)
+  if constexpr (KG == 2) {
+    if (ps_kgroup_combine<TM, TN, XCH, KV>(acc, smem_ps, wave, lane16, grp)) return;
+  }
   if (dbg & 16) {              // probe: no epilogue (one never-taken store keeps the accumulators live)
     float keep = 0.f;
 #pragma unroll
@@ -525,11 +588,11 @@ __global__ __launch_bounds__(64 * NWM * NWN, 2) void igemm_ps_kernel(const ldmk_
       ps_epilogue<TM, TN, TR, PL, true>(p, acc, m0 + wm * 32 * TM, n0 + wn * 32 * TN, splitk, ks, bz, ws, lane,
                                          reinterpret_cast<float*>(smem_ps) + wave * (32 * 33));
   } else {
-    if (lean == 1) ps_epilogue<TM, TN, TR, PL, false, 1>(p, acc, m0 + wm * 32 * TM, n0 + wn * 32 * TN, splitk, ks, bz, ws, lane);
-    else if (lean == 2) ps_epilogue<TM, TN, TR, PL, false, 2>(p, acc, m0 + wm * 32 * TM, n0 + wn * 32 * TN, splitk, ks, bz, ws, lane);
-    else if (lean == 3) ps_epilogue<TM, TN, TR, PL, false, 3>(p, acc, m0 + wm * 32 * TM, n0 + wn * 32 * TN, splitk, ks, bz, ws, lane);
-    else if (lean == 4) ps_epilogue<TM, TN, TR, PL, false, 4>(p, acc, m0 + wm * 32 * TM, n0 + wn * 32 * TN, splitk, ks, bz, ws, lane);
-    else ps_epilogue<TM, TN, TR, PL>(p, acc, m0 + wm * 32 * TM, n0 + wn * 32 * TN, splitk, ks, bz, ws, lane);
+    if (lean == 1) ps_epilogue<TM, TN, TR, PL, false, 1, KG == 2>(p, acc, m0 + wm * 32 * TM, n0 + wn * 32 * TN, splitk, ks, bz, ws, lane);
+    else if (lean == 2) ps_epilogue<TM, TN, TR, PL, false, 2, KG == 2>(p, acc, m0 + wm * 32 * TM, n0 + wn * 32 * TN, splitk, ks, bz, ws, lane);
+    else if (lean == 3) ps_epilogue<TM, TN, TR, PL, false, 3, KG == 2>(p, acc, m0 + wm * 32 * TM, n0 + wn * 32 * TN, splitk, ks, bz, ws, lane);
+    else if (lean == 4) ps_epilogue<TM, TN, TR, PL, false, 4, KG == 2>(p, acc, m0 + wm * 32 * TM, n0 + wn * 32 * TN, splitk, ks, bz, ws, lane);
+    else ps_epilogue<TM, TN, TR, PL, false, 0, KG == 2>(p, acc, m0 + wm * 32 * TM, n0 + wn * 32 * TN, splitk, ks, bz, ws, lane);
   }
 }
 
@@ -844,16 +907,23 @@ static const PsCfg kPsCfg[] = {{256, 160, false}, {256, 320, false}, {256, 256, 
                                {256, 160, false}, {256, 128, true},
                                // 8: 256x160, 9: 256x128, 10: 128x256 with FOUR waves of 64 x 160 / 64 x 128 and a 2-deep ring: two workgroups per
                                // CU, whose DMA issue / barrier / epilogue phases overlap the other one's matrix work
-                               {256, 160, false}, {256, 128, true}, {128, 256, true}};
+                               {256, 160, false}, {256, 128, true}, {128, 256, true},
+                               // 11: 256x320 (8 x 1 waves of 32 x 320), 12: 128x320 (4 x 1 waves of 32 x 320): a wave holds five (value, gate)
+                               // pairs; F16X2 planes only.  The GEGLU projections are 5120 / 2560 / 1280 wide: 320-wide tiles cover
+                               // them in 256 x k (11) or 512 x k (12) workgroups = whole rounds of the 256 CUs x 1 (11) or 2 (12)
+                               // workgroups per CU, where the 256-wide tiles leave 1.25 / 2.5 rounds.
+                               {256, 320, true}, {128, 320, true}};
+// pcfg kPsBases + b: base tile b with two K groups inside the workgroup (igemm_ps_kernel's KG = 2); b = 4 (128x160) and 12 (128x320) run
+constexpr int kPsBases = 13;
 
-template <int NWM, int NWN, int TM, int TN, int NS, bool TR, int PL = 3, bool KV = false>
+template <int NWM, int NWN, int TM, int TN, int NS, bool TR, int PL = 3, bool KV = false, int KG = 1>
 static int ps_launch(const ldmk_igemm_args& a, int splitk, float* ws, hipStream_t st) {
   constexpr int BM = 32 * TM * NWM, BN = 32 * TN * NWN;
-  constexpr size_t lds = (size_t)NS * (BM / 32 + BN / 32) * PL * 1024;
+  constexpr size_t lds = (size_t)KG * NS * (BM / 32 + BN / 32) * PL * 1024;      // (KG rings in the one dynamic array)
   static_assert(lds <= 160 * 1024, "LDS ring exceeds 160 KiB");
   static bool attr = false;
   if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(igemm_ps_kernel<NWM, NWN, TM, TN, NS, TR, PL, KV>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(igemm_ps_kernel<NWM, NWN, TM, TN, NS, TR, PL, KV, KG>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     attr = true;
   }
@@ -863,7 +933,7 @@ static int ps_launch(const ldmk_igemm_args& a, int splitk, float* ws, hipStream_
   const int nfast_env = switch_value(SW_PS_NFAST);
   const int lean_env = switch_value(SW_PS_LEAN);     // (0: the general epilogue everywhere, A/B)
   const int nfast = (nfast_env && (a.N + BN - 1) / BN > 1 && (a.M + BM - 1) / BM >= 8 ? 1 : 0) | (lean_env ? 0 : 2);   // (a few row tiles only: the old order)
-  hipLaunchKernelGGL((igemm_ps_kernel<NWM, NWN, TM, TN, NS, TR, PL, KV>), dim3(tiles, splitk, a.batch > 1 ? a.batch : 1), dim3(64 * NWM * NWN), lds,
+  hipLaunchKernelGGL((igemm_ps_kernel<NWM, NWN, TM, TN, NS, TR, PL, KV, KG>), dim3(tiles, splitk, a.batch > 1 ? a.batch : 1), dim3(64 * NWM * NWN * KG), lds,
                      st, a, splitk, ws, dbg, nfast);
   if (splitk > 1 && !a.raw_slabs) return launch_splitk_reduce(a, splitk, ws, st);
   return check_launch("ldmk_igemm(ps)");
@@ -899,10 +969,13 @@ static int pw_launch(const ldmk_igemm_args& a, int splitk, float* ws, hipStream_
 // chunk, unrolled, so the tap of a stage -- hence the VGPR holding its offsets -- is a compile-time index, and 18 % NS == 0
 // keeps the ring buffer index static too.  Same products in the same order into every accumulator as igemm_kernel<BF = 4> on
 // tile_cfg 5 / 1: bitwise equal at equal splitk (a K split must fall on chunk boundaries: splitk divides C / 32).
-template <int NWM, int NWN, int TM, int TN, bool TR>
-__global__ __launch_bounds__(64 * NWM * NWN, 2) void igemm_psc_kernel(const ldmk_igemm_args p, const int splitk, float* __restrict__ ws, const int nfast) {
+// KG = 2: the K groups of igemm_ps_kernel, here on the 32-channel chunks (C / 32 even, as splitk = 2 asks: both groups run the same
+// number of stages).
+template <int NWM, int NWN, int TM, int TN, bool TR, int KG = 1>
+__global__ __launch_bounds__(64 * NWM * NWN * KG, KG == 1 ? 2 : 1) void igemm_psc_kernel(const ldmk_igemm_args p, const int splitk, float* __restrict__ ws, const int nfast) {
   constexpr int PL = 2, NS = 3;
   constexpr int NW = NWM * NWN;
+  static_assert(KG == 1 || (KG == 2 && NW == 4), "K groups: two groups of a four-wave tile");
   constexpr int BM = 32 * TM * NWM, BN = 32 * TN * NWN;
   constexpr int FA = BM / 32, FB = BN / 32, U = FA + FB;
   constexpr int UHI = (U + NW - 1) / NW, ULO = U / NW;
@@ -910,9 +983,12 @@ __global__ __launch_bounds__(64 * NWM * NWN, 2) void igemm_psc_kernel(const ldmk
   constexpr int UB = PL * 1024;
   constexpr int STAGE = U * UB;
   static_assert(18 % NS == 0 && PL * UHI * (NS - 1) <= 63, "ring / vmcnt");
-  extern __shared__ __attribute__((aligned(1024))) unsigned char smem_ps[];
+  constexpr int XFIT = NS * STAGE * KG / (NW * 4096), XCH = KG == 1 ? 1 : (TM * TN < XFIT ? TM * TN : XFIT);
+  static_assert(XCH >= 1, "the hand-over of group 1's accumulators needs room for a tile per wave");
+  extern __shared__ __attribute__((aligned(1024))) unsigned char smem_ps[];      // [KG][NS][STAGE]
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int tid = threadIdx.x, lane = tid & 63, wave_all = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int grp = KG == 1 ? 0 : wave_all / NW, wave = wave_all - grp * NW;       // (K group, wave within the group)
   const int l31 = lane & 31, half = lane >> 5;
   const int wm = wave / NWN, wn = wave - wm * NWN;
   const int tiles_m = (p.M + BM - 1) / BM;
@@ -924,8 +1000,8 @@ __global__ __launch_bounds__(64 * NWM * NWN, 2) void igemm_psc_kernel(const ldmk
 
   const int C = p.c0;
   const int nc32 = C / 32;
-  const int c_per = (nc32 + splitk - 1) / splitk;
-  const int c_begin = ks * c_per;
+  const int c_per = KG == 1 ? (nc32 + splitk - 1) / splitk : nc32 / KG;      // (KG = 2: splitk == 1, group g takes slice g)
+  const int c_begin = (KG == 1 ? ks : grp) * c_per;
   const int c_end = min(nc32, c_begin + c_per);
   const int Kb_in = C / 16, Kb_w = p.K / 16;
   const int Nb = p.N / 32;
@@ -961,7 +1037,8 @@ __global__ __launch_bounds__(64 * NWM * NWN, 2) void igemm_psc_kernel(const ldmk
     ubase[i] = (u >= FA && u < U && blk < Nb) ? (unsigned)blk * (unsigned)Kb_w * (unsigned)UB + (unsigned)(18 * c_begin) * (unsigned)UB : PS_OOB;
   }
   const unsigned lane16 = lane * 16;
-  const unsigned lds0 = (unsigned)(size_t)smem_ps;
+  unsigned char* const ring = smem_ps + grp * (NS * STAGE);      // this group's ring
+  const unsigned lds0 = (unsigned)(size_t)ring;
   const bool hi_wave = wave + NW * (UHI - 1) < U;
 
   f32x16 acc[TM][TN];
@@ -1001,7 +1078,7 @@ __global__ __launch_bounds__(64 * NWM * NWN, 2) void igemm_psc_kernel(const ldmk
       asm volatile("s_barrier" ::: "memory");
       issue(j + 2 < 18 ? c : c + 1, (j + 2) % 18, (j + 2) % NS, sB + 2);
       ++sB;
-      const unsigned char* sb = smem_ps + (j % NS) * STAGE + lane16;
+      const unsigned char* sb = ring + (j % NS) * STAGE + lane16;
       f16x8 a8[PL][TM];
 #pragma unroll
       for (int g = 0; g < PL; ++g)
@@ -1029,12 +1106,15 @@ __global__ __launch_bounds__(64 * NWM * NWN, 2) void igemm_psc_kernel(const ldmk
     }
   }
   wait_vm<0>();
+  if constexpr (KG == 2) {
+    if (ps_kgroup_combine<TM, TN, XCH, false>(acc, smem_ps, wave, lane16, grp)) return;
+  }
   const int lean = ps_lean_form<TR>(p, splitk, (nfast & 2) != 0, m0 + (wm + 1) * 32 * TM, n0 + (wn + 1) * 32 * TN);
-  if (lean == 1) ps_epilogue<TM, TN, TR, PL, false, 1>(p, acc, m0 + wm * 32 * TM, n0 + wn * 32 * TN, splitk, ks, 0, ws, lane);
-  else if (lean == 2) ps_epilogue<TM, TN, TR, PL, false, 2>(p, acc, m0 + wm * 32 * TM, n0 + wn * 32 * TN, splitk, ks, 0, ws, lane);
-  else if (lean == 3) ps_epilogue<TM, TN, TR, PL, false, 3>(p, acc, m0 + wm * 32 * TM, n0 + wn * 32 * TN, splitk, ks, 0, ws, lane);
-  else if (lean == 4) ps_epilogue<TM, TN, TR, PL, false, 4>(p, acc, m0 + wm * 32 * TM, n0 + wn * 32 * TN, splitk, ks, 0, ws, lane);
-  else ps_epilogue<TM, TN, TR, PL>(p, acc, m0 + wm * 32 * TM, n0 + wn * 32 * TN, splitk, ks, 0, ws, lane);
+  if (lean == 1) ps_epilogue<TM, TN, TR, PL, false, 1, KG == 2>(p, acc, m0 + wm * 32 * TM, n0 + wn * 32 * TN, splitk, ks, 0, ws, lane);
+  else if (lean == 2) ps_epilogue<TM, TN, TR, PL, false, 2, KG == 2>(p, acc, m0 + wm * 32 * TM, n0 + wn * 32 * TN, splitk, ks, 0, ws, lane);
+  else if (lean == 3) ps_epilogue<TM, TN, TR, PL, false, 3, KG == 2>(p, acc, m0 + wm * 32 * TM, n0 + wn * 32 * TN, splitk, ks, 0, ws, lane);
+  else if (lean == 4) ps_epilogue<TM, TN, TR, PL, false, 4, KG == 2>(p, acc, m0 + wm * 32 * TM, n0 + wn * 32 * TN, splitk, ks, 0, ws, lane);
+  else ps_epilogue<TM, TN, TR, PL, false, 0, KG == 2>(p, acc, m0 + wm * 32 * TM, n0 + wn * 32 * TN, splitk, ks, 0, ws, lane);
 }
 
 // GroupNorm scale / shift [+ SiLU] of (the channel concat of) x0 | x1 written ONCE as the [n hw][C] matrix in the F16X2 form of
@@ -1072,28 +1152,41 @@ __global__ __launch_bounds__(256) void gn_apply_ps_h2_kernel(const float* __rest
   *reinterpret_cast<f16x8*>(d + 1024) = f16x8{l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
 }
 
-template <int NWM, int NWN, int TM, int TN, bool TR>
+template <int NWM, int NWN, int TM, int TN, bool TR, int KG = 1>
 static int psc_launch(const ldmk_igemm_args& a, int splitk, float* ws, hipStream_t st) {
   constexpr int BM = 32 * TM * NWM, BN = 32 * TN * NWN;
-  constexpr size_t lds = (size_t)3 * (BM / 32 + BN / 32) * 2048;
+  constexpr size_t lds = (size_t)KG * 3 * (BM / 32 + BN / 32) * 2048;
   static_assert(lds <= 160 * 1024, "LDS ring exceeds 160 KiB");
   static bool attr = false;
   if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(igemm_psc_kernel<NWM, NWN, TM, TN, TR>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(igemm_psc_kernel<NWM, NWN, TM, TN, TR, KG>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     attr = true;
   }
   const int tiles = ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN);
   const int nfast_env = switch_value(SW_PS_NFAST);
   const int lean_env = switch_value(SW_PS_LEAN);
   const int nfast = (nfast_env && (a.N + BN - 1) / BN > 1 && (a.M + BM - 1) / BM >= 8 ? 1 : 0) | (lean_env ? 0 : 2);
-  hipLaunchKernelGGL((igemm_psc_kernel<NWM, NWN, TM, TN, TR>), dim3(tiles, splitk, 1), dim3(64 * NWM * NWN), lds, st, a, splitk, ws, nfast);
+  hipLaunchKernelGGL((igemm_psc_kernel<NWM, NWN, TM, TN, TR, KG>), dim3(tiles, splitk, 1), dim3(64 * NWM * NWN * KG), lds, st, a, splitk, ws, nfast);
   if (splitk > 1 && !a.raw_slabs) return launch_splitk_reduce(a, splitk, ws, st);
   return check_launch("ldmk_igemm(ps, conv)");
 }
 
-const char* igemm_ps_unsupported(const ldmk_igemm_args& a, int pcfg, int splitk) {
+const char* igemm_ps_unsupported(const ldmk_igemm_args& a, int pcfg_in, int splitk) {
   if (a.compute != LDMK_COMPUTE_BF16X3 && a.compute != LDMK_COMPUTE_F16X2) return "the pre-split tiles run the bf16x3 and the f16x2 arithmetic (compute)";
   const int pl = a.compute == LDMK_COMPUTE_F16X2 ? 2 : 3;
+  const bool kg = pcfg_in >= kPsBases;            // two K groups inside the workgroup
+  const int pcfg = kg ? pcfg_in - kPsBases : pcfg_in;
+  if (kg) {
+    if (pcfg == 0 || pcfg == 1 || pcfg == 2 || pcfg == 3 || pcfg == 5 || pcfg == 11)
+      return "K groups inside the workgroup: not on an eight-wave tile (16 waves would leave 128 registers each); tile_cfg 40 (128x160) and 48 (128x320) only";
+    if (pcfg != 4 && pcfg != 12) return "K groups inside the workgroup: tile_cfg 40 (128x160) and 48 (128x320) only";
+    if (splitk != 1) return "K groups inside the workgroup take the place of split-K: splitk must be 1";
+    if (a.a_mode == LDMK_A_CONV3X3 && (a.c0 / 32) % 2) return "conv mode with K groups: C_in / 32 must be even (the groups split K on 32-channel chunk boundaries)";
+  }
+  if (pcfg == 11 || pcfg == 12) {
+    if (pl != 2) return "the 320-wide tiles (34 / 35) exist in the f16x2 arithmetic only (three bf16 planes at this width do not fit)";
+    if (a.a_mode != LDMK_A_ROWS || a.attn_kv_out) return "the 320-wide tiles (34 / 35): rows mode, no fused QKV tiles";
+  }
   if (pl == 2 && (pcfg == 6 || pcfg == 7)) return "the warp-specialised pre-split tiles (29 / 30) exist in the bf16x3 arithmetic only";
   if (pl == 2 && a.out_ps && !a.range_flag) return "out_ps in the f16x2 arithmetic needs range_flag";
   if (!a.a_ps || !a.w_ps) return "a_ps / w_ps (operands in the PS layout: ldmk_pack_ps, ldmk_ln_stats_ps, out_ps of a producer GEMM)";
@@ -1113,15 +1206,17 @@ const char* igemm_ps_unsupported(const ldmk_igemm_args& a, int pcfg, int splitk)
   if (a.a_tf != LDMK_TF_NONE && a.a_tf != LDMK_TF_LAYERNORM_FOLDED) return "no staging prologue: a_ps is what gets multiplied";
   if (a.K % 32 || a.N % 32) return "K and N must be multiples of 32";
   if (a.a_ps1) {      // two A sources: columns [0, a_ps_k0) from a_ps, [a_ps_k0, K) from a_ps1 (igemm_ps_kernel only)
-    if (a.a_mode != LDMK_A_ROWS || pcfg == 6 || pcfg == 7) return "a_ps1: rows mode on tile_cfg 23..28 / 31..33 (not the conv-mode or warp-specialised tiles)";
+    if (a.a_mode != LDMK_A_ROWS || pcfg == 6 || pcfg == 7) return "a_ps1: rows mode on tile_cfg 23..28 / 31..35 / 40 / 48 (not the conv-mode or warp-specialised tiles)";
     if (a.batch > 1 || a.attn_kv_out || a.a_tf != LDMK_TF_NONE || a.epi == LDMK_EPI_GEGLU)
       return "a_ps1: no batching, no fused QKV tiles, no folded LayerNorm, no GEGLU";
+    if (kg && pcfg == 12) return "a_ps1: not on the 128x320 tile with K groups (tile_cfg 48)";
     if (a.a_ps_k0 <= 0 || a.a_ps_k0 >= a.K || a.a_ps_k0 % 32) return "a_ps1: a_ps_k0 and K - a_ps_k0 must be positive multiples of 32";
   }
   const long long kb = a.K / 16;
   if ((a.a_mode == LDMK_A_ROWS && (long long)((a.M + 31) / 32) * kb * pl * 1024 >= (1LL << 31)) || (long long)(a.N / 32) * kb * pl * 1024 >= (1LL << 31))
     return "an operand of 2 GiB or more";
-  if (a.epi == LDMK_EPI_GEGLU && (!kPsCfg[pcfg].even_tn || splitk > 1)) return "GEGLU needs a tile of (value, gate) pairs (256x256, 128x256) and no split-K";
+  if (a.epi == LDMK_EPI_GEGLU && (a.N / 32) % 2) return "GEGLU: an odd count of 32-column tiles (N must be a multiple of 64: (value, gate) pairs of tiles)";
+  if (a.epi == LDMK_EPI_GEGLU && (!kPsCfg[pcfg].even_tn || splitk > 1)) return "GEGLU needs a tile of (value, gate) pairs (256x256, 128x256, 256x320, 128x320) and no split-K";
   if (splitk > a.K / 32) return "more K slices than 32-deep chunks";
   if (a.out_ps) {
     if (splitk > 1 || a.batch > 1 || a.stats_out) return "out_ps: no split-K, no batching, no GroupNorm records (transposed epilogue)";
@@ -1131,7 +1226,7 @@ const char* igemm_ps_unsupported(const ldmk_igemm_args& a, int pcfg, int splitk)
   }
   if (a.stats_out && !a.out) return "stats_out needs out";
   if (a.attn_kv_out) {
-    if (pl != 2 || (pcfg != 0 && pcfg != 4)) return "attn_kv_out: the F16X2 arithmetic on tile_cfg 23 / 27";
+    if (pl != 2 || (pcfg != 0 && pcfg != 4)) return "attn_kv_out: the F16X2 arithmetic on tile_cfg 23 / 27 / 40";
     if (a.stats_out || splitk > 1 || a.batch > 1 || a.epi != LDMK_EPI_NONE || a.out_ps || !a.out || !a.range_flag)
       return "attn_kv_out: the fused QKV projection (no split-K / batching / GEGLU / records / out_ps; out and range_flag required)";
     if (a.attn_heads <= 0 || a.N != 3 * 32 * a.attn_heads) return "attn_kv_out: N must be 3 x 32 x attn_heads ([q | k | v] of d_head 32)";
@@ -1143,6 +1238,15 @@ const char* igemm_ps_unsupported(const ldmk_igemm_args& a, int pcfg, int splitk)
 int igemm_ps_dispatch(const ldmk_igemm_args& a, int pcfg, int splitk, float* ws, hipStream_t st) {
   // the transposed epilogue serves every call but those that want GroupNorm records
   const bool tr = !a.stats_out;
+  if (pcfg >= kPsBases) {                      // two K groups inside the workgroup (unsupported() admits bases 4 and 12, splitk 1)
+    if (pcfg - kPsBases == 12)                 // 128x320, F16X2 rows mode: GEGLU with a second wave per SIMD
+      return tr ? ps_launch<4, 1, 1, 10, 2, true, 2, false, 2>(a, splitk, ws, st) : ps_launch<4, 1, 1, 10, 2, false, 2, false, 2>(a, splitk, ws, st);
+    if (a.a_mode == LDMK_A_CONV3X3) return tr ? psc_launch<4, 1, 1, 5, true, 2>(a, splitk, ws, st) : psc_launch<4, 1, 1, 5, false, 2>(a, splitk, ws, st);
+    if (a.compute == LDMK_COMPUTE_F16X2 && a.attn_kv_out) return ps_launch<4, 1, 1, 5, 3, true, 2, true, 2>(a, splitk, ws, st);
+    if (a.compute == LDMK_COMPUTE_F16X2)
+      return tr ? ps_launch<4, 1, 1, 5, 3, true, 2, false, 2>(a, splitk, ws, st) : ps_launch<4, 1, 1, 5, 3, false, 2, false, 2>(a, splitk, ws, st);
+    return tr ? ps_launch<4, 1, 1, 5, 2, true, 3, false, 2>(a, splitk, ws, st) : ps_launch<4, 1, 1, 5, 2, false, 3, false, 2>(a, splitk, ws, st);
+  }
   if (a.a_mode == LDMK_A_CONV3X3) {            // (unsupported() admits F16X2 on pcfg 0 / 1 / 3 / 4)
     switch (pcfg) {
       case 0: return tr ? psc_launch<8, 1, 1, 5, true>(a, splitk, ws, st) : psc_launch<8, 1, 1, 5, false>(a, splitk, ws, st);
@@ -1163,6 +1267,8 @@ int igemm_ps_dispatch(const ldmk_igemm_args& a, int pcfg, int splitk, float* ws,
       case 8: return tr ? ps_launch<4, 1, 2, 5, 3, true, 2>(a, splitk, ws, st) : ps_launch<4, 1, 2, 5, 3, false, 2>(a, splitk, ws, st);
       case 9: return tr ? ps_launch<4, 1, 2, 4, 3, true, 2>(a, splitk, ws, st) : ps_launch<4, 1, 2, 4, 3, false, 2>(a, splitk, ws, st);
       case 10: return tr ? ps_launch<2, 2, 2, 4, 3, true, 2>(a, splitk, ws, st) : ps_launch<2, 2, 2, 4, 3, false, 2>(a, splitk, ws, st);
+      case 11: return tr ? ps_launch<8, 1, 1, 10, 3, true, 2>(a, splitk, ws, st) : ps_launch<8, 1, 1, 10, 3, false, 2>(a, splitk, ws, st);
+      case 12: return tr ? ps_launch<4, 1, 1, 10, 2, true, 2>(a, splitk, ws, st) : ps_launch<4, 1, 1, 10, 2, false, 2>(a, splitk, ws, st);
       default: return tr ? ps_launch<4, 2, 1, 4, 3, true, 2>(a, splitk, ws, st) : ps_launch<4, 2, 1, 4, 3, false, 2>(a, splitk, ws, st);
     }
   }

@@ -72,6 +72,55 @@ __device__ __forceinline__ void gn_tile_record(const float (&vals)[16], float* s
   }
 }
 
+// The same record with the three sums taken over the tile's 32 rows ONE AFTER THE OTHER, rows 0..31 -- the order of
+// igemm_reduce_stats_kernel (igemm.hip), which writes the records of a launch split over workgroups.  The K groups inside the
+// workgroup (igemm_ps.hip, KG = 2) promise the bits of that two-launch form, records included, so that a shape may move between
+// the two without its GroupNorm changing.  Rows 8 g + 4 half + e sit at vals[4 g + e]: the running sum crosses between the half-
+// waves eight times, each crossing one v_permlane32_swap (both halves then hold the sending half's value).
+__device__ __forceinline__ float gn_other_half(float x, const bool from_upper) {
+  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
+  return __uint_as_float(from_upper ? r[1] : r[0]);
+}
+__device__ __forceinline__ void gn_tile_record_rows(const float (&vals)[16], float* stats_out, const int tile_row, const int N,
+                                                    const int col, const int l31, const int half) {
+#pragma clang fp contract(off)
+  float tsum = 0.f;
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) tsum += vals[4 * g + e];           // (meaningful in the lower half)
+    tsum = gn_other_half(tsum, false);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) tsum += vals[4 * g + e];           // (meaningful in the upper half)
+    tsum = gn_other_half(tsum, true);
+  }
+  const float shift = tsum * (1.0f / 32.0f);
+  float sm = 0.f, sq = 0.f;
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float d = vals[4 * g + e] - shift;
+      sm += d;
+      sq = fmaf(d, d, sq);
+    }
+    sm = gn_other_half(sm, false);
+    sq = gn_other_half(sq, false);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float d = vals[4 * g + e] - shift;
+      sm += d;
+      sq = fmaf(d, d, sq);
+    }
+    sm = gn_other_half(sm, true);
+    sq = gn_other_half(sq, true);
+  }
+  if (half == 0) {
+    float* d = stats_out + ((long long)tile_row * N + col) * 3;
+    d[0] = shift; d[1] = sm; d[2] = sq;
+  }
+}
+
 // split-K: the raw partial slab [ks][M][N]; igemm_reduce_kernel or the consumer (raw_slabs) sums them
 template <int TM, int TN>
 __device__ __forceinline__ void col_slab_store(const ldmk_igemm_args& p, const f32x16 (&acc)[TM][TN], const int rowbase, const int colbase,
@@ -140,7 +189,7 @@ __device__ __forceinline__ void col_geglu(const ldmk_igemm_args& p, const f32x16
 // the GroupNorm record.  Element offsets are 32-bit (the host checks M * ldc < 2^31): one add per address; the per-sample vector
 // is looked up once per 32-row tile when a tile cannot straddle two samples (rows_per_sample % 32 == 0: every UNet / VQGAN
 // level) instead of one integer division per output element.  (acc is scratch here: the folded LayerNorm rewrites it.)
-template <int TM, int TN>
+template <int TM, int TN, bool ROWREC = false>      // ROWREC: the record in row order (gn_tile_record_rows)
 __device__ __forceinline__ void col_general(const ldmk_igemm_args& p, f32x16 (&acc)[TM][TN], const int rowbase, const int colbase,
                                             const int bz, const int l31, const int half, const bool lnf) {
   float* __restrict__ outp = p.out + (long long)bz * p.out_bstride;
@@ -183,7 +232,10 @@ __device__ __forceinline__ void col_general(const ldmk_igemm_args& p, f32x16 (&a
         }
         vals[r] = v;
       }
-      if (p.stats_out && rowbase + i * 32 < p.M) gn_tile_record(vals, p.stats_out, (rowbase + i * 32) >> 5, p.N, col, l31, half);
+      if (p.stats_out && rowbase + i * 32 < p.M) {
+        if constexpr (ROWREC) gn_tile_record_rows(vals, p.stats_out, (rowbase + i * 32) >> 5, p.N, col, l31, half);
+        else gn_tile_record(vals, p.stats_out, (rowbase + i * 32) >> 5, p.N, col, l31, half);
+      }
     }
   }
 }
@@ -193,7 +245,7 @@ __device__ __forceinline__ void col_general(const ldmk_igemm_args& p, f32x16 (&a
 // own basic block and waits for itself (577 s_waitcnt in the 160 -> 160 convolution's kernel); here the 16 residuals of a tile
 // are asked for at once -- and the operand set is a template argument: 1 = per-sample vector, 2 = residual, 3 = neither,
 // 4 = both.  Same arithmetic, rounding by rounding, as the general form.
-template <int TM, int TN, int LEAN>
+template <int TM, int TN, int LEAN, bool ROWREC = false>
 __device__ __forceinline__ void col_lean(const ldmk_igemm_args& p, const f32x16 (&acc)[TM][TN], const int rowbase, const int colbase,
                                          const int bz, const int l31, const int half) {
   static_assert(LEAN >= 1 && LEAN <= 4, "operand set 1..4");
@@ -224,7 +276,10 @@ __device__ __forceinline__ void col_lean(const ldmk_igemm_args& p, const f32x16 
         else vals[r] = col_finish(t, bv, vec, extra[r]);
         outp[obase + (unsigned)(((r & 3) + 8 * (r >> 2)) * p.ldc)] = vals[r];
       }
-      if (p.stats_out) gn_tile_record(vals, p.stats_out, (rowbase + i * 32) >> 5, p.N, col, l31, half);
+      if (p.stats_out) {
+        if constexpr (ROWREC) gn_tile_record_rows(vals, p.stats_out, (rowbase + i * 32) >> 5, p.N, col, l31, half);
+        else gn_tile_record(vals, p.stats_out, (rowbase + i * 32) >> 5, p.N, col, l31, half);
+      }
     }
   }
 }

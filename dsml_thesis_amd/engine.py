@@ -36,11 +36,16 @@ def plan_key(a, m):
 #   "f16x2"      plans measured in the F16X2 arithmetic itself; a shape listed under "bf16x3" only runs in F16X2 too, on that tile
 #   "ps_bf16x3"  shapes measured faster on the pre-split tiles (csrc/igemm_ps.hip: operands in the PS layout, LDS-DMA), bf16x3 planes
 #   "ps_f16x2"   the same for the two-plane F16X2 form of the pre-split tiles
+#   "ps_f16x2_wg" rows of "ps_f16x2" measured faster, inside the step, on a form that decomposes the problem differently INSIDE the
+#                workgroup (tile_cfg 34 / 35: 320-wide wave tiles, 40 / 48: two K groups): the tile for exactly the measured row
+#                count, taken only where "ps_f16x2" offers a plan at all (that section keeps the route decision and every other batch)
 # Keys are plan_key() strings "M,N,K,a_mode,a_tf,epi,batch[,bt][,s<stride>u<upsample>]"; loaded as {rest of key: [(M, cfg, splitk)]}.
 # A/B overrides: LDMK_PLAN_TABLE / LDMK_X3_TABLE / LDMK_H2_TABLE / LDMK_PS_TABLE / LDMK_PS_H2_TABLE name a file that replaces ONE
 # section -- either a flat {key: [cfg, splitk]} file (what the tuning tools write) or another merged file, whose section is taken.
+# "ps_f16x2_wg" goes with "ps_f16x2": a flat LDMK_PS_H2_TABLE file IS the pre-split F16X2 plan (no "_wg" rows), a merged one brings its
+# own "_wg" section or none -- so a copy of another commit's "ps_f16x2" section reproduces that commit's launches.
 _SECTIONS = {"f32": "LDMK_PLAN_TABLE", "bf16x3": "LDMK_X3_TABLE", "f16x2": "LDMK_H2_TABLE", "ps_bf16x3": "LDMK_PS_TABLE",
-             "ps_f16x2": "LDMK_PS_H2_TABLE"}
+             "ps_f16x2": "LDMK_PS_H2_TABLE", "ps_f16x2_wg": "LDMK_PS_H2_TABLE"}
 _TABLES = {}
 _PLAN_FILE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "igemm_plans.json")
 
@@ -95,6 +100,8 @@ def table(section):
                 raw = {}
             if any(k in raw for k in _SECTIONS):      # a merged file: this section of it
                 raw = raw.get(section, {})
+            elif section == "ps_f16x2_wg":            # a flat file: the "ps_f16x2" section, whole
+                raw = {}
             for k, (cfg, sk) in raw.items():
                 m, rest = k.split(",", 1)
                 t.setdefault(rest, []).append((int(m), int(cfg), int(sk)))
@@ -195,7 +202,10 @@ def ps_plan(rest, m, h2=False, max_ratio=None, far=False):
     """(cfg, splitk) of the pre-split plan for the shape key `rest` ("N,K,mode,tf,epi,batch") at m rows, or None.  h2: the section
     of the F16X2 form."""
     sec = "ps_f16x2" if h2 else "ps_bf16x3"
-    return lookup(sec, rest, m, max_ratio) if max_ratio is not None else choose(sec, rest, m, far)
+    p = lookup(sec, rest, m, max_ratio) if max_ratio is not None else choose(sec, rest, m, far)
+    if p is not None and h2:      # the in-workgroup decomposition measured faster at exactly this row count
+        p = lookup("ps_f16x2_wg", rest, m, 1.0) or p
+    return p
 
 
 # select_plan's inputs and result.  PlanPolicy: what the OWNER of a launch program decides -- h2_flag: the site's F16X2 range flag

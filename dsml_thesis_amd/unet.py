@@ -351,7 +351,7 @@ def emit_spatial_transformer(nb_, ctx_pg, P, sd, prefix, m, x, h, w, L_ctx, ctx_
             else:
                 pg.add("ldmk_ln_stats_ps", p_(x2d), rows, C_, 1e-5, p_(stats), p_(xs), LN_GUARD_RATIO, p_(ln_flag))
             kw = {}
-            if attn_kv is not None and h2_flag is not None and int(plan[0]) in (23, 27) and int(plan[1]) <= 1:
+            if attn_kv is not None and h2_flag is not None and int(plan[0]) in (23, 27, 40) and int(plan[1]) <= 1:
                 # the fused QKV projection writes K / V straight as the attention's pre-split tiles (no fp32 K / V, no pre-pass)
                 kw["attn_kv"] = attn_kv
                 kv_state["tiles"] = attn_kv[0]

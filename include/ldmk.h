@@ -135,10 +135,15 @@ typedef struct ldmk_igemm_args {
                                 inside the workgroup: 2x1x4, 2x2x4, 1x1x4, 1x2x4, 1x1x8, 1x1x16, 2x1x8, 1x2x8; needs
                                 w_frag; stride-1 3x3 convolutions and rows mode), 21..22 = pin a warp-specialised tile of
                                 the LDMK_COMPUTE_BF16X3 arithmetic (csrc/igemm_ws.hip: 256x160 / 256x128, four consumer +
-                                four producer waves; bitwise the results of tile_cfg 5 / 1 at equal splitk), 23..33 = pin a
+                                four producer waves; bitwise the results of tile_cfg 5 / 1 at equal splitk), 23..48 = pin a
                                 pre-split tile (csrc/igemm_ps.hip: 23..28 = 256x160, 256x320, 256x256, 128x320, 128x160,
                                 128x256; 29 / 30 = the warp-specialised 256x160 / 256x128 with four consumer + four LDS-DMA
                                 waves; 31..33 = 256x160, 256x128, 128x256 on four waves with 2x2 / 2x4 wave tiles;
+                                34 / 35 = 256x320 / 128x320 with 32x320 wave tiles holding (value, gate) pairs, F16X2
+                                only, bitwise 28's results; 36..48 = tiles 23..35 with two K groups inside the
+                                workgroup, of which 40 (= 27's, 128x160) and 48 (= 35's, 128x320) run, at splitk = 1,
+                                and the rest are refused: bitwise the base tile at splitk = 2, with every
+                                epilogue of splitk = 1;
                                 needs a_ps and w_ps, see the end of this struct).  The K-summation
                                 order depends on (tile_cfg, splitk), so a caller that needs results that are
                                 bitwise independent of the batch size pins both (ldmk_igemm_plan)          */

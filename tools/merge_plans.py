@@ -1,4 +1,4 @@
-"""The ONE plan file (dsml_thesis_amd/igemm_plans.json: sections f32 / bf16x3 / f16x2 / ps_bf16x3 / ps_f16x2, see engine.py) and the
+"""The ONE plan file (dsml_thesis_amd/igemm_plans.json: sections f32 / bf16x3 / f16x2 / ps_bf16x3 / ps_f16x2 / ps_f16x2_wg, see engine.py) and the
 flat {key: [tile_cfg, splitk]} files the tuning tools write and the LDMK_*_TABLE overrides read.
    python tools/merge_plans.py --extract f16x2 gpurun_out/plans_f16x2.json      # a section as a flat file (a sweep's starting point)
    python tools/merge_plans.py --merge f16x2 gpurun_out/plans_f16x2.json        # a flat file's entries into that section
@@ -10,7 +10,7 @@ import os
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PLAN_FILE = os.path.join(ROOT, "dsml_thesis_amd", "igemm_plans.json")
-SECTIONS = ("f32", "bf16x3", "f16x2", "ps_bf16x3", "ps_f16x2")
+SECTIONS = ("f32", "bf16x3", "f16x2", "ps_bf16x3", "ps_f16x2", "ps_f16x2_wg")
 
 
 def load():

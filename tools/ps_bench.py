@@ -1,4 +1,4 @@
-"""Isolated timing of the pre-split bf16x3 tiles (csrc/igemm_ps.hip, tile_cfg 23..28) against the LDS-tiled / warp-specialised
+"""Isolated timing of the pre-split bf16x3 tiles (csrc/igemm_ps.hip, tile_cfg 23..35, 40, 48) against the LDS-tiled / warp-specialised
 bf16x3 forms on the GEMM shapes of the 64x64x4, B = 16 step.  Operand copies are rotated between launches so that no launch
 finds its A rows in the L2 that just read them (as inside the step).   python tools/ps_bench.py [--quick]"""
 import sys
@@ -73,7 +73,8 @@ def main():
         flops = 2.0 * B * M * N * K
         res = {}
         cands = [(1 if geglu else 5, 1)] if probe else [(1 if geglu else 5, 1), (22 if geglu else 21, 1)]
-        pcands = [(25, 1), (28, 1), (30, 1), (32, 1), (33, 1)] if geglu else [(23, 1), (24, 1), (26, 1), (27, 1), (29, 1), (31, 1)]
+        # (34 / 35: the 320-wide GEGLU tiles, 48: 35 with two K groups in the workgroup -- F16X2 only; 40: 27 with two K groups)
+        pcands = [(25, 1), (28, 1), (30, 1), (32, 1), (33, 1), (34, 1), (35, 1), (48, 1)] if geglu else [(23, 1), (24, 1), (26, 1), (27, 1), (29, 1), (31, 1), (40, 1)]
         if not geglu and M * N <= 4096 * 640 and K >= 640:
             cands += [(5, 2), (5, 4)]
             pcands += [(23, 2), (23, 4), (27, 2), (27, 4), (29, 2), (29, 4), (31, 2), (31, 4)]
