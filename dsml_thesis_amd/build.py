@@ -13,7 +13,7 @@ from . import switches
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = switches.get("LDMK_LIB_OUT") or os.path.join(HERE, "libldmk.so")      # (LDMK_LIB_OUT: an A/B build next to the shipped one)
-SOURCES = ["igemm.hip", "rgemm.hip", "norms.hip", "attention.hip", "small.hip", "wgrad.hip", "backward.hip", "attention_train.hip", "winograd.hip", "post.hip", "sgemm.hip", "attention_small.hip", "attention_bf16.hip", "igemm_ws.hip", "igemm_ps.hip", "ddim_diff.hip", "patches.hip", "posterior.hip", "vq_train.hip", "kl_train.hip", "objective.hip", "classifier.hip", "dpm.hip"]
+SOURCES = ["igemm.hip", "rgemm.hip", "norms.hip", "attention.hip", "small.hip", "wgrad.hip", "backward.hip", "attention_train.hip", "winograd.hip", "post.hip", "sgemm.hip", "attention_small.hip", "attention_bf16.hip", "igemm_ws.hip", "igemm_ps.hip", "ddim_diff.hip", "patches.hip", "posterior.hip", "vq_train.hip", "kl_train.hip", "objective.hip", "classifier.hip", "dpm.hip", "lpips.hip"]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wno-unused-value", "-Wno-unused-result"]
 # probe builds only (tools/ps_probe.sh, tools/pw_stamps.py: LDMK_HIPCC_FLAGS=-DLDMK_PS_PROBES): extra flags are part of the digest
 FLAGS += switches.get("LDMK_HIPCC_FLAGS", "").split()

@@ -241,6 +241,13 @@ _SIGS = {
     "ldmk_cross_entropy": (C.c_int, [_fp, _fp, _fp, _fp, _fp, C.c_float, C.c_int, C.c_int, _fp]),
     "ldmk_relu": (C.c_int, [_fp, _fp, C.c_longlong, _fp]),
     "ldmk_relu_bwd": (C.c_int, [_fp, _fp, _fp, C.c_longlong, _fp]),
+    # ---- LPIPS over VGG16: the kernels around the convolutions
+    "ldmk_lpips_conv_in": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, _fp]),
+    "ldmk_lpips_conv_in_bwd": (C.c_int, [_fp, _fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, _fp]),
+    "ldmk_relu_maxpool2": (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
+    "ldmk_relu_maxpool2_bwd": (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
+    "ldmk_lpips_layer": (C.c_int, [_fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp]),
+    "ldmk_lpips_layer_bwd": (C.c_int, [_fp, _fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
 }
 # every symbol include/ldmk.h declares (checked by tests/test_abi.py against the header text)
 EXPORTED = [k for k in _SIGS if k not in ("ldmk_igemm_force_config", "ldmk_attn_force_qt")]

@@ -2,10 +2,12 @@
 (ldm/modules/losses/contperceptual.py:7-110); the PatchGAN of both (taming/modules/discriminator/model.py:17-67).
 
 `VQLPIPSWithDiscriminator` turns a reconstruction into the image gradient `FirstStageTrainer.backward` takes.  The pixel
-term runs on ldmk_l1_grad / ldmk_mse_grad; the PatchGAN discriminator and the perceptual network are plain torch modules on
-PyTorch-ROCm autograd (well under 1 % of the step), the arrangement the CLIP / ArcFace losses of the fine-tuning models have.
-The perceptual network is injected: pretrained LPIPS weights cannot be obtained offline, so `perceptual_weight > 0` without
-a module is refused.
+term runs on ldmk_l1_grad / ldmk_mse_grad; the PatchGAN discriminator is a plain torch module on PyTorch-ROCm autograd, the
+arrangement the CLIP / ArcFace losses of the fine-tuning models have.  The perceptual network is injected: pretrained LPIPS
+weights cannot be obtained offline, so `perceptual_weight > 0` without a module is refused.  `dsml_thesis_amd.lpips.LPIPS` is
+the real one (VGG16, value and image gradient on HIP, weights from local files; DESIGN §25 has its cost: 3 % of a KL-f4
+step); `StandInPerceptual` below is what the fixtures inject, and only of that stand-in is it true that the perceptual
+term is well under 1 % of the step.
 
 One backward per autoencoder step:
     loss    = nll + d_weight * disc_factor * g + codebook_weight * qloss,   nll = mean(pixel + perceptual_weight * p)
@@ -149,7 +151,10 @@ def _perceptual_module(name, perceptual_loss, perceptual_weight):
     if perceptual_weight > 0:
         raise NotImplementedError(f"{name}: perceptual_weight > 0 needs a perceptual network, and the "
                                   "pretrained LPIPS weights cannot be obtained offline: pass one as perceptual_loss=<module> "
-                                  "(inputs, reconstructions) -> (n,1,1,1), or set perceptual_weight=0")
+                                  "(inputs, reconstructions) -> (n,1,1,1) -- dsml_thesis_amd.lpips.LPIPS(vgg_ckpt=..., lpips_ckpt=...) "
+                                  "is LPIPS on HIP from local weight files, also as perceptual_loss={target: "
+                                  "taming.modules.losses.lpips.LPIPS, params: {vgg_ckpt: ..., lpips_ckpt: ...}} -- or set "
+                                  "perceptual_weight=0")
     return None
 
 

@@ -481,8 +481,9 @@ def set_split(a, w_ptr=None):
 
 
 def conv3x3(x, wp, bias=None, x1=None, stride=1, pad_lo=1, upsample=False, coef=None, silu=True, batch_vec=None,
-            residual=None, out=None, out_hw=None, compute=0, range_flag=None):
-    """x: (n,h,w,c0) [+ x1 (n,h,w,c1) channel-concat]; wp: [9*(c0+c1)][cout] -> (n,oh,ow,cout)."""
+            residual=None, out=None, out_hw=None, compute=0, range_flag=None, splitk_ws=None):
+    """x: (n,h,w,c0) [+ x1 (n,h,w,c1) channel-concat]; wp: [9*(c0+c1)][cout] -> (n,oh,ow,cout).  splitk_ws: a float scratch the
+    planner may split K into (None: it plans without one, i.e. no split)."""
     n, h, w_, c0 = x.shape
     c1 = 0 if x1 is None else x1.shape[-1]
     cout = wp.shape[1]
@@ -500,7 +501,7 @@ def conv3x3(x, wp, bias=None, x1=None, stride=1, pad_lo=1, upsample=False, coef=
     a = make_igemm_args(n * oh * ow, cout, 9 * (c0 + c1), x, c0, wp, out, cout, oh * ow, a1=x1, c1=c1,
                         conv=(h, w_, oh, ow, stride, pad_lo, 1 if upsample else 0), tf=tf, tf_coef=coef, bias=bias,
                         batch_vec=batch_vec, batch_vec_ld=0 if batch_vec is None else batch_vec.stride(0),
-                        residual=residual, compute=compute, range_flag=range_flag)
+                        residual=residual, compute=compute, range_flag=range_flag, splitk_ws=splitk_ws)
     igemm(a)
     return out
 

@@ -71,6 +71,31 @@ def load_recipe(module, gain=1.0, seed=0):
     return new
 
 
+# VGG16 `features` indices of the thirteen convolutions per LPIPS slice, with (cin, cout): the reference's `net.slice{k}.{i}` keys
+LPIPS_VGG = ((1, ((0, 3, 64), (2, 64, 64))), (2, ((5, 64, 128), (7, 128, 128))), (3, ((10, 128, 256), (12, 256, 256), (14, 256, 256))),
+             (4, ((17, 256, 512), (19, 512, 512), (21, 512, 512))), (5, ((24, 512, 512), (26, 512, 512), (28, 512, 512))))
+LPIPS_CHNS = (64, 128, 256, 512, 512)
+LPIPS_SHIFT, LPIPS_SCALE = (-.030, -.088, -.188), (.458, .448, .450)
+
+
+def lpips_state_dict(seed=0, use_dropout=True):
+    """A synthetic LPIPS state dict with the reference's keys (taming/modules/losses/lpips.py), drawn in key order from ONE
+    RandomState(seed): convolution weights He-normal N(0, sqrt(2 / (9 cin))), biases N(0, 0.05), lin weights U(0, 1); the
+    ScalingLayer buffers hold their constants.  14.7 M parameters: generated where they are needed, never stored in a fixture."""
+    rs = np.random.RandomState(seed)
+    sd = OrderedDict()
+    sd["scaling_layer.shift"] = torch.tensor(LPIPS_SHIFT, dtype=torch.float32)[None, :, None, None]
+    sd["scaling_layer.scale"] = torch.tensor(LPIPS_SCALE, dtype=torch.float32)[None, :, None, None]
+    for k, convs in LPIPS_VGG:
+        for i, cin, cout in convs:
+            w = rs.standard_normal((cout, cin, 3, 3)) * np.sqrt(2.0 / (9 * cin))
+            sd[f"net.slice{k}.{i}.weight"] = torch.from_numpy(w.astype(np.float32))
+            sd[f"net.slice{k}.{i}.bias"] = torch.from_numpy((rs.standard_normal(cout) * 0.05).astype(np.float32))
+    for k, c in enumerate(LPIPS_CHNS):
+        sd[f"lin{k}.model.{1 if use_dropout else 0}.weight"] = torch.from_numpy(rs.uniform(0.0, 1.0, (1, c, 1, 1)).astype(np.float32))
+    return sd
+
+
 def fr_config(unet=None, vq=None):
     unet, vq = unet or FR_UNET, vq or VQ_F4
     return dict(

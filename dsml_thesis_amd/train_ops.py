@@ -118,7 +118,7 @@ def pack_dgrad3x3(wp, cin, cout, out=None):
     return out
 
 
-def conv3x3_dgrad(dy, wd, in_hw, stride=1, out=None, residual=None, pad_lo=1):
+def conv3x3_dgrad(dy, wd, in_hw, stride=1, out=None, residual=None, pad_lo=1, compute=None, splitk_ws=None):
     """Data gradient of a 3x3 convolution: dy (n,oh,ow,cout), wd = pack_dgrad3x3 weights [9*cout][cin] ->
     (n,h,w,cin).  stride 2 reads dy zero-inserted (ldmk_igemm upsample=2).  pad_lo is the FORWARD convolution's: 1 is the
     pad-1 form; 0 with stride 2 is the encoder's Downsample, F.pad(x, (0,1,0,1)) then a pad-0 convolution (model.py:72-76).
@@ -131,8 +131,8 @@ def conv3x3_dgrad(dy, wd, in_hw, stride=1, out=None, residual=None, pad_lo=1):
         raise ValueError(f"conv3x3_dgrad: pad_lo={pad_lo}, stride={stride}: pad_lo is 1, or 0 with stride 2")
     if out is None:
         out = _f32(n, h, w_, cin, device=dy.device)
-    a = ops.make_igemm_args(n * h * w_, cin, 9 * cout, dy, cout, wd, out, cin, h * w_, compute=COMPUTE,
-                            conv=(oh, ow, h, w_, 1, 2 - pad_lo, 2 if stride == 2 else 0), residual=residual)
+    a = ops.make_igemm_args(n * h * w_, cin, 9 * cout, dy, cout, wd, out, cin, h * w_, compute=COMPUTE if compute is None else compute,
+                            conv=(oh, ow, h, w_, 1, 2 - pad_lo, 2 if stride == 2 else 0), residual=residual, splitk_ws=splitk_ws)
     ops.igemm(a)
     return out
 
@@ -568,6 +568,115 @@ def relu_bwd(x, dy, out=None):
     out = torch.empty_like(x) if out is None else out
     L.call("ldmk_relu_bwd", _ptr(x), _ptr(dy), _ptr(out), x.numel(), stream())
     return out
+
+
+# ---- LPIPS over VGG16 (csrc/lpips.hip): the kernels around the convolutions; fp32 whatever COMPUTE says
+def lpips_conv_in(x, wt, bias, shift, scale, out=None):
+    """conv1_1 behind the ScalingLayer: x (n,3,h,w) NCHW, wt (64,3,3,3) OIHW -> relu(conv((x - shift) / scale) + bias), (n,h,w,64) NHWC."""
+    for name, t in (("x", x), ("wt", wt), ("bias", bias), ("shift", shift), ("scale", scale), ("out", out)):
+        ops._chk(t, f"lpips_conv_in {name}")
+    if x.dim() != 4 or x.shape[1] != 3 or wt.numel() != 64 * 27 or bias.numel() != 64 or shift.numel() != 3 or scale.numel() != 3:
+        raise ValueError(f"lpips_conv_in: x {tuple(x.shape)}, wt {tuple(wt.shape)}, bias {tuple(bias.shape)}: (n,3,h,w), (64,3,3,3), (64,)")
+    n, _, h, w_ = x.shape
+    out = _f32(n, h, w_, 64, device=x.device) if out is None else out
+    if out.numel() != n * h * w_ * 64:
+        raise ValueError(f"lpips_conv_in: out {tuple(out.shape)} for x {tuple(x.shape)}")
+    L.call("ldmk_lpips_conv_in", _ptr(x), _ptr(wt), _ptr(bias), _ptr(shift), _ptr(scale), _ptr(out), n, h, w_, stream())
+    return out
+
+
+def lpips_conv_in_bwd(dy, y, wt, scale, dx=None):
+    """dy, y (n,h,w,64) NHWC (y: the saved output, the ReLU mask) -> dx (n,3,h,w) NCHW, every element written."""
+    for name, t in (("dy", dy), ("y", y), ("wt", wt), ("scale", scale), ("dx", dx)):
+        ops._chk(t, f"lpips_conv_in_bwd {name}")
+    if dy.dim() != 4 or dy.shape[-1] != 64 or y.shape != dy.shape or wt.numel() != 64 * 27 or scale.numel() != 3:
+        raise ValueError(f"lpips_conv_in_bwd: dy {tuple(dy.shape)}, y {tuple(y.shape)}, wt {tuple(wt.shape)}")
+    n, h, w_, _ = dy.shape
+    dx = _f32(n, 3, h, w_, device=dy.device) if dx is None else dx
+    if dx.numel() != n * 3 * h * w_:
+        raise ValueError(f"lpips_conv_in_bwd: dx {tuple(dx.shape)} for dy {tuple(dy.shape)}")
+    L.call("ldmk_lpips_conv_in_bwd", _ptr(dy), _ptr(y), _ptr(wt), _ptr(scale), _ptr(dx), n, h, w_, stream())
+    return dx
+
+
+def relu_maxpool2(x, relu_out=None, pooled=None):
+    """x (n,h,w,c) NHWC pre-activations -> (pooled (n,h//2,w//2,c), relu_out).  relu_out: None (not written), True (a fresh map),
+    or a buffer -- x itself is allowed and makes the ReLU in place."""
+    ops._chk(x, "relu_maxpool2 x")
+    n, h, w_, c = x.shape
+    if relu_out is True:
+        relu_out = torch.empty_like(x)
+    pooled = _f32(n, h // 2, w_ // 2, c, device=x.device) if pooled is None else pooled
+    ops._chk(relu_out, "relu_maxpool2 relu_out")
+    ops._chk(pooled, "relu_maxpool2 pooled")
+    if (relu_out is not None and relu_out.shape != x.shape) or tuple(pooled.shape) != (n, h // 2, w_ // 2, c):
+        raise ValueError(f"relu_maxpool2: x {tuple(x.shape)}, pooled {tuple(pooled.shape)}")
+    L.call("ldmk_relu_maxpool2", _ptr(x), _ptr(relu_out), _ptr(pooled), n, h, w_, c, stream())
+    return pooled, relu_out
+
+
+def relu_maxpool2_bwd(x, dy, dx=None):
+    """x (n,h,w,c): the map the forward read or the post-ReLU map it wrote; dy (n,h//2,w//2,c) -> dx like x, every element written."""
+    ops._chk(x, "relu_maxpool2_bwd x")
+    ops._chk(dy, "relu_maxpool2_bwd dy")
+    n, h, w_, c = x.shape
+    if tuple(dy.shape) != (n, h // 2, w_ // 2, c):
+        raise ValueError(f"relu_maxpool2_bwd: dy {tuple(dy.shape)} for x {tuple(x.shape)}")
+    dx = torch.empty_like(x) if dx is None else dx
+    ops._chk(dx, "relu_maxpool2_bwd dx")
+    if dx.shape != x.shape:
+        raise ValueError(f"relu_maxpool2_bwd: dx {tuple(dx.shape)} for x {tuple(x.shape)}")
+    L.call("ldmk_relu_maxpool2_bwd", _ptr(x), _ptr(dy), _ptr(dx), n, h, w_, c, stream())
+    return dx
+
+
+def _lpips_layer_dims(f0, f1, lin, what):
+    for name, t in (("f0", f0), ("f1", f1), ("lin", lin)):
+        ops._chk(t, f"{what} {name}")
+    c = f0.shape[-1]
+    n = f0.shape[0]
+    if f0.dim() < 3 or f1.shape != f0.shape or lin.numel() != c:
+        raise ValueError(f"{what}: taps {tuple(f0.shape)} / {tuple(f1.shape)}, lin {tuple(lin.shape)}: two (n, ..., C) maps and C weights")
+    return n, f0[0].numel() // c, c
+
+
+_LPIPS_PARTIALS = {}     # device -> float64 scratch of ldmk_lpips_layer's per-workgroup partials (64 per sample), stream-ordered reuse
+
+
+def lpips_layer(f0, f1, lin, res=None, accumulate=False):
+    """res[b] (+)= mean over the pixels of sum_c lin_c (u0_c - u1_c)^2, u = f / (|f| + 1e-10): f0, f1 (n,h,w,C) or (n,hw,C) NHWC."""
+    n, hw, c = _lpips_layer_dims(f0, f1, lin, "lpips_layer")
+    if res is None:
+        if accumulate:
+            raise ValueError("lpips_layer: accumulate needs res")
+        res = _f32(n, device=f0.device)
+    ops._chk(res, "lpips_layer res")
+    if res.numel() != n:
+        raise ValueError(f"lpips_layer: res {tuple(res.shape)} for n={n}")
+    scratch = _LPIPS_PARTIALS.get(f0.device)
+    if scratch is None or scratch.numel() < 64 * n:
+        scratch = _LPIPS_PARTIALS[f0.device] = torch.empty(max(64 * n, 4096), device=f0.device, dtype=torch.float64)
+    L.call("ldmk_lpips_layer", _ptr(f0), _ptr(f1), _ptr(lin), _ptr(res), 1 if accumulate else 0, n, hw, c, _ptr(scratch), stream())
+    return res
+
+
+def lpips_layer_bwd(fa, fb, lin, g, df=None, relu_mask=True, accumulate=False):
+    """The gradient of lpips_layer with respect to fa, its first tap (the other branch: swap the taps), for g (n,) = dL / dres.
+    relu_mask: zero where fa <= 0 (fa is a post-ReLU map; the result is the pre-activation's gradient); accumulate: added to df."""
+    n, hw, c = _lpips_layer_dims(fa, fb, lin, "lpips_layer_bwd")
+    ops._chk(g, "lpips_layer_bwd g")
+    if g.numel() != n:
+        raise ValueError(f"lpips_layer_bwd: g {tuple(g.shape)} for n={n}")
+    if df is None:
+        if accumulate:
+            raise ValueError("lpips_layer_bwd: accumulate needs df")
+        df = torch.empty_like(fa)
+    ops._chk(df, "lpips_layer_bwd df")
+    if df.shape != fa.shape:
+        raise ValueError(f"lpips_layer_bwd: df {tuple(df.shape)} for fa {tuple(fa.shape)}")
+    L.call("ldmk_lpips_layer_bwd", _ptr(fa), _ptr(fb), _ptr(lin), _ptr(g), _ptr(df), 1 if relu_mask else 0, 1 if accumulate else 0,
+           n, hw, c, stream())
+    return df
 
 
 def adamw_(p, g, m, v, lr, betas, eps, weight_decay, step):

@@ -14,6 +14,8 @@ TARGET_MAP = {
     "taming.modules.losses.vqperceptual.VQLPIPSWithDiscriminator": "dsml_thesis_amd.losses.VQLPIPSWithDiscriminator",
     "ldm.modules.losses.contperceptual.LPIPSWithDiscriminator": "dsml_thesis_amd.losses.LPIPSWithDiscriminator",
     "ldm.modules.losses.LPIPSWithDiscriminator": "dsml_thesis_amd.losses.LPIPSWithDiscriminator",
+    "taming.modules.losses.lpips.LPIPS": "dsml_thesis_amd.lpips.LPIPS",
+    "ldm.modules.losses.lpips.LPIPS": "dsml_thesis_amd.lpips.LPIPS",
     "ldm.models.autoencoder.AutoencoderKL": "dsml_thesis_amd.autoencoder.AutoencoderKL",
     "ldm.models.autoencoder.IdentityFirstStage": "dsml_thesis_amd.autoencoder.IdentityFirstStage",
     "ldm.models.diffusion.ddpm.LatentDiffusion": "dsml_thesis_amd.ddpm.LatentDiffusion",

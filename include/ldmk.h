@@ -956,6 +956,32 @@ int ldmk_cross_entropy(const float* logits, const long long* target, float* per_
 int ldmk_relu(const float* x, float* y, long long n, void* stream);
 int ldmk_relu_bwd(const float* x, const float* dy, float* dx, long long n, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * LPIPS over VGG16 (taming/modules/losses/lpips.py), value and image gradient (csrc/lpips.hip): the memory-bound kernels around
+ * the 3x3 convolutions, which run on ldmk_igemm.  fp32, no float atomics, bitwise reproducible; activations NHWC.
+ * conv1_1 with the ScalingLayer applied on load: x (n,3,h,w) NCHW, wt (64,3,3,3) OIHW, bias (64), shift / scale (3) ->
+ * out (n,h,w,64) = relu(conv3x3_pad1((x - shift[c]) / scale[c]) + bias); the zero padding is of the scaled tensor.
+ * Backward: dy (n,h,w,64) and y, the saved output (mask y > 0) -> dx (n,3,h,w) NCHW, the division by scale[c] included. */
+int ldmk_lpips_conv_in(const float* x, const float* wt, const float* bias, const float* shift, const float* scale, float* out, int n,
+                       int h, int w, void* stream);
+int ldmk_lpips_conv_in_bwd(const float* dy, const float* y, const float* wt, const float* scale, float* dx, int n, int h, int w,
+                           void* stream);
+/* ReLU then MaxPool2d(2, 2) of x (n,h,w,c), h, w >= 2: pooled (n, h/2, w/2, c); an odd trailing row or column is dropped.  relu_out
+ * non-NULL: the full-resolution post-ReLU map as well (it may be x itself).  Backward: x is the pre-activation or the post-ReLU map,
+ * dy (n, h/2, w/2, c) -> dx (n,h,w,c), every element written: dy goes to the first maximum in row-major window order (strict >) and
+ * only where x > 0 there; everything else, dropped rows and columns included, is 0. */
+int ldmk_relu_maxpool2(const float* x, float* relu_out, float* pooled, int n, int h, int w, int c, void* stream);
+int ldmk_relu_maxpool2_bwd(const float* x, const float* dy, float* dx, int n, int h, int w, int c, void* stream);
+/* One LPIPS layer over two NHWC taps f0, f1 (n, hw, c), c in {64, 128, 256, 512}, lin (c) the 1x1 weight, all 16-byte aligned:
+ *   u_i = f_i / (sqrt(sum_c f_i^2) + 1e-10);  res[b] (+)= (1 / hw) sum_pixels sum_c lin_c (u0_c - u1_c)^2     (accumulate: +=)
+ * scratch = 64 n doubles.  Backward with respect to fa, the FIRST tap (the other branch: swap the taps), g (n) = dL / dres:
+ *   a_c = 2 lin_c (ua_c - ub_c) g[b] / hw,  r = 1 / (na + 1e-10),  df_k = r a_k - fa_k (sum_c a_c fa_c) / (na (na + 1e-10)^2)
+ * and df = r a where na = 0 (torch autograd gives NaN there).  relu_mask: df_k = 0 where fa_k <= 0; accumulate: added to df. */
+int ldmk_lpips_layer(const float* f0, const float* f1, const float* lin, float* res, int accumulate, int n, int hw, int c,
+                     double* scratch, void* stream);
+int ldmk_lpips_layer_bwd(const float* fa, const float* fb, const float* lin, const float* g, float* df, int relu_mask, int accumulate,
+                         int n, int hw, int c, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
